@@ -11,10 +11,15 @@ round-robin (global block b -> rank b % N), no collectives on the data path
 (only the timing barrier / max-over-ranks reduction).  ``scaling`` is weak.
 
 Prints ONE JSON line (rank 0).  ``roofline`` is computed from HIP events
-recorded on the stream the kernel runs on; ``cpu_baseline`` times the CPU
+recorded on the stream the kernel runs on.  A plain run sets up, warms up,
+times the K steps and prints the line.  ``--full`` adds the legs that take
+runs of their own after the timed region: ``cpu_baseline`` times the CPU
 restatement of the crate's AVX2 loop (oracle/, test infrastructure) on a
 bounded sample of the same workload and checks the GPU parity of those sampled
-blocks bit-for-bit.
+blocks bit-for-bit; the host-path probe (``per_rank[r].host_probe``); and the
+codec configs' round trip (``roofline.round_trip_bit_exact``).
+``--dump-outputs DIR`` writes what the last timed step computed as
+``DIR/<name>.npy`` (dump_outputs).
 """
 from __future__ import annotations
 
@@ -61,7 +66,17 @@ def parse():
     ap.add_argument("--config", default="encode83", choices=sorted(CONFIGS))
     ap.add_argument("--blocks", type=int, default=0, help="blocks per GPU (default: 1024 for 1 MiB, 512 for 4 MiB, 64 for 16 MiB blocks)")
     ap.add_argument("--tune", default="", help="kernel knobs, e.g. 'chunks=2,grid=0' (default: library defaults)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the legs beyond the headline figure: the cpu_baseline "
+                         "leg (with its bit-for-bit check of the GPU's sampled blocks), the host-path probe and, "
+                         "for codec configs, the round trip; --no-cpu / --no-host-probe take single legs out again")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed (parity shards of an encode, "
+                         "rebuilt shards of a decode) as DIR/<name>.npy, float32 / float64, at most 48 MiB in all: "
+                         "every byte of a small batch, otherwise a fixed seeded sample of columns of every shard "
+                         "plus every shard's byte sum; same arguments, same inputs, so two builds compare output "
+                         "for output")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=1.5, help="wall budget of the cpu_baseline sample")
     ap.add_argument("--backend", default="gloo", choices=["gloo", "nccl"],
                     help="process group for the timing barrier / max-over-ranks only (the data path "
@@ -113,7 +128,7 @@ def parse():
                          "DIR/rank<r>.npz, for a test-side check against the CPU oracle")
     ap.add_argument("--dump-blocks", type=int, default=2)
     ap.add_argument("--no-host-probe", action="store_true",
-                    help="skip the untimed host-path probe after the timed region (mapped Block-Cache blocks coded "
+                    help="--full: skip the untimed host-path probe after the timed region (mapped Block-Cache blocks coded "
                          "zero-copy on this rank's GPU; rank 0 also over every visible GPU from one process)")
     ap.add_argument("--launch-check", action="store_true",
                     help="launcher rehearsal without a GPU: ranks join the process group, exchange their "
@@ -730,21 +745,23 @@ def run(args):
     if args.layout == "ptrs":
         # pointer-table calls of the timed steps that ran as a slot grid (strided kernels)
         out["config"]["ptr_table_grid_calls_timed"] = grid_calls
-    if shape.codec:
+    if args.dump_outputs:        # before any leg below touches the buffers again
+        dump_outputs(args, shape, w, f".rank{rank}" if world > 1 else "", world)
+    if shape.codec and args.full:
         out["roofline"]["round_trip_bit_exact"] = w.round_trip()
     if args.dump_dir and shape.erasures is None:
         dump_blocks(args, shape, w, rank, world)
-    # per-rank figures (the line's roofline is the slowest rank's) and the host-path probe
+    # per-rank figures (the line's roofline is the slowest rank's) and, with --full, the host-path probe
     mine = {"rank": rank, "device": dev.index, "ms_per_step": round(float(np.mean(step_ms)), 4),
             "frac": round(shape.algo_bytes_per_block * shape.B / (float(np.mean(step_ms)) / 1e3) / HBM_PEAK, 4)}
-    if not args.no_host_probe:
+    if args.full and not args.no_host_probe:
         mine["host_probe"] = host_probe(dev.index, all_devices=rank == 0)
     per_rank = [mine]
     if world > 1:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
     out["per_rank"] = per_rank
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_leg(args, shape, w)
     if rank == 0:
         emit(out)
@@ -784,9 +801,12 @@ def run_single(args):
                              "frac": round(shape.algo_bytes_per_block * shape.B / (float(np.mean(per_dev_ms[d])) / 1e3)
                                            / HBM_PEAK, 4)} for d in range(n)]}
     out = report(args, shape, n, ranks, elapsed, per_dev_ms[slowest], ramp_steps, "single", extra)
-    if shape.codec:
+    if args.dump_outputs:
+        for d, w in enumerate(works):
+            dump_outputs(args, shape, w, f".dev{d}" if n > 1 else "", n)
+    if shape.codec and args.full:
         out["roofline"]["round_trip_bit_exact"] = all(w.round_trip() for w in works)
-    if n == 1 and not args.no_cpu:
+    if n == 1 and args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_leg(args, shape, works[0])
     emit(out)
 
@@ -835,6 +855,51 @@ def dump_blocks(args, shape, w, rank, world):
     np.savez(os.path.join(args.dump_dir, f"rank{rank}.npz"),
              data=w.data[:n, :, :S].cpu().numpy(), parity=w.parity[:n, :, :S].cpu().numpy(),
              blocks=np.array(placement.weak_batch(shape.B, rank, world)[:n]), device=w.dev.index)
+
+
+DUMP_BYTES = 48 << 20      # --dump-outputs: all files of one run together stay under this
+
+
+def timed_outputs(shape, w):
+    """What a caller of the timed step receives, by name: [B, rows, >= S]
+    device arrays (only the first S bytes of a shard slot are output)."""
+    k = shape.k
+    if shape.erasures is None:
+        return {"parity": w.parity}
+    if w.rebuilt is not None:          # compact output, or the pointer tables' fresh buffers
+        rebuilt = w.rebuilt
+    else:                              # in place: the erased shards' own slots, in shard order
+        rebuilt = w.shards[w.erased].view(shape.B, shape.erasures, -1)
+    return {"parity": w.shards[:, k:], "rebuilt": rebuilt} if shape.codec else {"rebuilt": rebuilt}
+
+
+def dump_outputs(args, shape, w, tag, share):
+    """--dump-outputs: after the timed steps and before anything else touches
+    the buffers, every output array of the last step goes to DIR/<name>.npy as
+    float32 [B, rows, n]: all S bytes of every shard when that fits the budget,
+    otherwise the same n columns of every shard -- a sample drawn once from
+    SEED, always with the shard's last 256 bytes (the partial tail tile) -- and
+    DIR/<name>_sum.npy, float64 [B, rows], the exact byte sum of every whole
+    shard.  `share` runs (ranks or devices, told apart by `tag`) split the
+    budget."""
+    outs = timed_outputs(shape, w)
+    S = shape.S
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    with torch.cuda.device(w.dev), torch.cuda.stream(w.stream):
+        for name, arr in outs.items():
+            whole = arr[:, :, :S]
+            B, rows = whole.shape[0], whole.shape[1]
+            n = min(S, (DUMP_BYTES // share // len(outs) - 8 * B * rows - 4096) // (4 * B * rows))
+            if n < S:
+                tail = np.arange(S - min(256, n), S)
+                pick = np.random.default_rng(SEED).choice(S - len(tail), n - len(tail), replace=False)
+                cols = torch.from_numpy(np.sort(np.concatenate([pick, tail]))).to(w.dev)
+                sample = whole[:, :, cols]
+            else:
+                sample = whole
+            np.save(os.path.join(args.dump_outputs, f"{name}{tag}.npy"), sample.cpu().numpy().astype(np.float32))
+            np.save(os.path.join(args.dump_outputs, f"{name}_sum{tag}.npy"),
+                    whole.sum(dim=2, dtype=torch.int64).cpu().numpy().astype(np.float64))
 
 
 def traffic_key(args) -> str:

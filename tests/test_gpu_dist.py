@@ -79,7 +79,8 @@ def test_bench_self_launch_eight_ranks(gpu, tmp_path):
     is 8 x B blocks round-robin, and every rank's coded blocks equal the
     oracle's (each rank dumps its first blocks after the timed region)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--blocks", "4", "--steps", "3",
-           "--warmup", "1", "--ramp-seconds", "0.05", "--no-cpu", "--dump-dir", str(tmp_path), "--dump-blocks", "2"]
+           "--warmup", "1", "--ramp-seconds", "0.05", "--full", "--no-cpu", "--dump-dir", str(tmp_path),
+           "--dump-blocks", "2"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240, env=_env())
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
