@@ -75,7 +75,8 @@ def test_pool_alloc_free_rules(gpu):
         shmr_amd.ShardPool(0, 4096, 4)
 
 
-@pytest.mark.parametrize("k,p,S", [(8, 3, 65536), (10, 4, 12345 * 4 + 2), (4, 2, 4096 * 2)])
+@pytest.mark.parametrize("k,p,S", [(8, 3, 65536), (10, 4, 12345 * 4 + 2), (4, 2, 4096 * 2),
+                                   (5, 5, 4096 + 48), (10, 6, 8192 + 48)])   # p > 4: a second row group
 def test_pool_churn_encode_and_rebuild(gpu, k, p, S):
     """Rounds of churn (random frees and allocs), then an encode and an
     in-place rebuild of every live block (random erasures, mixed patterns) in
