@@ -127,6 +127,15 @@ int shmr_ec_encode(shmr_ec_t* rs, uint8_t* const* shards, const size_t* shard_le
 int shmr_ec_reconstruct(shmr_ec_t* rs, uint8_t* const* shards, const size_t* shard_lens,
                         const uint8_t* present, size_t nshards, int data_only);
 
+/* ReedSolomon::verify.  The crate's checks, in its order, as shmr_ec_encode
+ * (count, EMPTY_SHARD, INCORRECT_SHARD_SIZE), before any device work.
+ * *consistent = 1 if shards[data..total) equal the parity of shards[0..data),
+ * else 0.  No shard is written.  The block is gathered into device scratch
+ * (grown without a free on the call path) and checked there by the kernel of
+ * shmr_ec_verify_batch_dev; blocking. */
+int shmr_ec_verify(shmr_ec_t* rs, uint8_t* const* shards, const size_t* shard_lens,
+                   size_t nshards, int* consistent);
+
 /* Asynchronous forms of shmr_ec_encode / shmr_ec_reconstruct (same arguments,
  * validation and errors, returned by the start call), so a Block Cache can
  * overlap its file I/O or copies with the GPU: when every shard the call
@@ -247,6 +256,21 @@ int shmr_ec_capture_reserve(int device, size_t bytes);
 int shmr_ec_encode_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_shard_pitch,
                              size_t data_block_pitch, uint8_t* d_parity, size_t parity_shard_pitch,
                              size_t parity_block_pitch, size_t nblocks, size_t shard_len,
+                             int device, void* stream);
+
+/* ReedSolomon::verify of nblocks blocks: a device-resident batch, addressed
+ * exactly as shmr_ec_encode_batch_dev.
+ * d_mismatch: nblocks uint32 words of DEVICE memory on `device` (4-byte
+ * aligned), overwritten: 0 = block b is a codeword; else bit min(r, 31) is set
+ * for every parity row r whose stored bytes differ from the recomputed ones
+ * in [0, shard_len).  Nothing else is written: the kernels read the data and
+ * the stored parity once ((data + parity) * shard_len bytes per block) and
+ * store only to the word of a block that differs.  Stream-ordered, capturable
+ * (the zeroing of d_mismatch is part of the enqueued work). */
+int shmr_ec_verify_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_shard_pitch,
+                             size_t data_block_pitch, const uint8_t* d_parity,
+                             size_t parity_shard_pitch, size_t parity_block_pitch,
+                             size_t nblocks, size_t shard_len, uint32_t* d_mismatch,
                              int device, void* stream);
 
 /* Reconstruct nblocks blocks in place.  All total shards of block b live at
@@ -521,7 +545,8 @@ enum {
     SHMR_EC_DEV_CAPTURE_RELEASED = 9,     /* ... and returned when their graph was destroyed */
     SHMR_EC_DEV_PTR_TABLE_GRIDS = 10,     /* *_ptrs_dev calls whose table named a slot grid and ran
                                              through the strided kernels (no table) */
-    SHMR_EC_DEV_COUNTERS = 11
+    SHMR_EC_DEV_BLOCKS_VERIFIED = 11,     /* blocks checked by shmr_ec_verify / shmr_ec_verify_batch_dev */
+    SHMR_EC_DEV_COUNTERS = 12
 };
 int shmr_ec_device_stats(int device, uint64_t* out, size_t n);
 

@@ -52,6 +52,11 @@ SIGNATURES = [
     ("shmr_ec_encode_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _sz, _sz,
       ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_verify", ctypes.c_int,
+     [ctypes.c_void_p, _u8pp, ctypes.POINTER(_sz), _sz, ctypes.POINTER(ctypes.c_int)]),
+    ("shmr_ec_verify_batch_dev", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _sz, _sz, ctypes.c_void_p,
+      ctypes.c_int, ctypes.c_void_p]),
     ("shmr_ec_reconstruct_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_int, ctypes.c_int,
       ctypes.c_void_p]),

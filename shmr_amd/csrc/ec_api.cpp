@@ -691,6 +691,43 @@ int shmr_ec_reconstruct(shmr_ec_t* rs, uint8_t* const* shards, const size_t* sha
     return reconstruct_impl(rs, shards, shard_lens, present, nshards, data_only, nullptr, nullptr);
 }
 
+// ---- host-buffer verify (ReedSolomon::verify) ---------------------------------------
+// The block is gathered into pooled device staging (a pitch layout; the pool
+// grows without freeing) with the result word behind it, checked by the batch
+// kernels, and the word copied back.
+int shmr_ec_verify(shmr_ec_t* rs, uint8_t* const* shards, const size_t* shard_lens, size_t nshards,
+                   int* consistent) {
+    return guarded([&]() -> int {
+        size_t len = 0;
+        int rc = check_encode(rs, shards, shard_lens, nshards, &len);
+        if (rc) return rc;
+        if (!consistent) return SHMR_EC_INVALID_ARGUMENT;
+        Codec& c = *rs->codec;
+        const unsigned k = c.k(), t = k + c.p();
+        const int dev = rs->device;
+        rc = core::check_device(dev);
+        if (rc) return rc;
+        core::DeviceScope scope(dev);
+        if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
+        const uint64_t pitch = core::round_up(len, 256);
+        core::StagingLease lease;
+        lease.s = core::StagingPool::get().acquire(dev, pitch * t + 256, &rc);
+        if (!lease.s) return rc;
+        core::Staging& s = *lease.s;
+        for (unsigned i = 0; i < t; ++i)
+            SHMR_HIP_TRY(hipMemcpyAsync(s.dbuf + i * pitch, shards[i], len, hipMemcpyHostToDevice, s.stream));
+        uint32_t* d_word = reinterpret_cast<uint32_t*>(s.dbuf + pitch * t);
+        const core::Layout L{s.dbuf, s.dbuf + k * pitch, 0, pitch, 0, pitch, k};
+        rc = core::verify_on_device(c, dev, L, 1, len, d_word, s.stream);
+        if (rc) return rc;
+        uint32_t word = 0;
+        SHMR_HIP_TRY(hipMemcpyAsync(&word, d_word, sizeof(word), hipMemcpyDeviceToHost, s.stream));
+        SHMR_HIP_TRY(core::sync_stream(s.stream));
+        *consistent = word == 0;
+        return SHMR_EC_OK;
+    });
+}
+
 int shmr_ec_encode_dev(shmr_ec_t* rs, uint8_t* const* d_shards, const size_t* shard_lens, size_t nshards,
                        int device) {
     return encode_dev_impl(rs, d_shards, shard_lens, nshards, device, nullptr);
@@ -800,6 +837,27 @@ int shmr_ec_encode_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_s
         const core::Layout L{d_data, d_parity, data_block_pitch, data_shard_pitch, parity_block_pitch, parity_shard_pitch,
                              c.k()};
         return core::encode_on_device(c, device, L, nblocks, shard_len, static_cast<hipStream_t>(stream));
+    });
+}
+
+int shmr_ec_verify_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_shard_pitch, size_t data_block_pitch,
+                             const uint8_t* d_parity, size_t parity_shard_pitch, size_t parity_block_pitch,
+                             size_t nblocks, size_t shard_len, uint32_t* d_mismatch, int device, void* stream) {
+    return guarded([&]() -> int {
+        if (!rs) return SHMR_EC_INVALID_ARGUMENT;
+        if (nblocks == 0) return SHMR_EC_OK;
+        if (shard_len == 0) return SHMR_EC_EMPTY_SHARD;
+        if (!d_data || !d_parity || !d_mismatch) return SHMR_EC_INVALID_ARGUMENT;
+        if (uintptr_t(d_mismatch) % alignof(uint32_t)) return SHMR_EC_INVALID_ARGUMENT;
+        int rc = core::check_device(device);
+        if (rc) return rc;
+        core::DeviceScope scope(device);
+        if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
+        Codec& c = *rs->codec;
+        // (the layout's output side is the stored parity: the verify kernels only read it)
+        const core::Layout L{d_data, const_cast<uint8_t*>(d_parity), data_block_pitch, data_shard_pitch,
+                             parity_block_pitch, parity_shard_pitch, c.k()};
+        return core::verify_on_device(c, device, L, nblocks, shard_len, d_mismatch, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -408,6 +408,14 @@ void permute_ptr_rows(const uint64_t* src, const uint8_t* present, size_t n, uns
 
 int grid_mode(OpClass op) { return g_tune[op].grid.load(); }
 
+int verify_chunks(unsigned rows) {
+#ifdef SHMR_EC_TOOLS
+    const int u = g_tune[kEncode].u.load();   // the tile-size A/B (tools/verify_ab.py --u-ab)
+    if (u == 1 || u == 2) return u;
+#endif
+    return kern::verify_chunks(rows);
+}
+
 uint64_t bounce_limit() { return uint64_t(g_bounce_kib.load()) << 10; }
 
 bool mirror_zero_copy() { return g_mirror_zc.load() != 0; }
@@ -1211,6 +1219,77 @@ int encode_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
     BlockSet bs;
     bs.n = nblocks;
     return launch_set(*c.encode_plan(), dev, L, bs, len, stream, kEncode);
+}
+
+// ===========================================================================
+// Parity check (ReedSolomon::verify).  The encode plan over the encode layout,
+// L.out_base being the stored parity: per group of <= 4 parity rows one
+// full-tile launch plus, when len is not a multiple of the tile, one launch
+// over the partial last tile -- split as launch_set splits an encode, without
+// its fused-tail and segment forms.  Misaligned shards take the same kernels
+// where the device serves unaligned vector access, else the byte-granular one.
+// ===========================================================================
+int verify_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint64_t len, uint32_t* d_mismatch,
+                     hipStream_t stream) {
+    int rc = device_init(dev, stream);
+    if (rc) return rc;
+    Plan& plan = *c.encode_plan();
+    if (nblocks == 0) return SHMR_EC_OK;
+    // (a memset node inside a capture: every replay starts from zero words)
+    SHMR_HIP_TRY(hipMemsetAsync(d_mismatch, 0, size_t(nblocks) * sizeof(uint32_t), stream));
+    const uint8_t* dplan = nullptr;
+    rc = plan_on_device(plan, dev, stream, false, &dplan);
+    if (rc) return rc;
+    count_device(dev, kDevBlocksVerified, nblocks);
+    const bool aligned16_all = aligned16(uintptr_t(L.in_base)) && aligned16(L.in_bpitch) && aligned16(L.in_spitch) &&
+                               aligned16(uintptr_t(L.out_base)) && aligned16(L.out_bpitch) && aligned16(L.out_spitch);
+    const bool aligned = aligned16_all || unaligned_vector(dev);
+    kern::ApplyArgs a{};
+    a.in_base = L.in_base;
+    a.out_base = L.out_base;
+    a.in_bpitch = L.in_bpitch;
+    a.in_spitch = L.in_spitch;
+    a.out_bpitch = L.out_bpitch;
+    a.out_spitch = L.out_spitch;
+    a.out_bias = L.out_bias;
+    a.blk_first = 0;
+    a.blk_stride = 1;
+    a.nblk = nblocks;
+    a.len = len;
+    a.k = plan.k;
+    a.m = plan.m;
+    a.plan = dplan;
+    a.tab_off = plan_tab_off(plan.k, plan.m);
+    a.in_identity = 1;
+    const uint64_t tb1 = kern::tile_bytes(1);
+    for (uint32_t row0 = 0; row0 < plan.m; row0 += kern::kMaxRowsPerLaunch) {
+        const uint32_t rows = std::min<uint32_t>(kern::kMaxRowsPerLaunch, plan.m - row0);
+        count_device(dev, kDevLaunches);
+        a.row0 = row0;
+        if (!aligned) {
+            a.col_base = 0;
+            a.tiles_per_block = uint32_t((len + tb1 - 1) / tb1);
+            a.ntiles = nblocks * a.tiles_per_block;
+            SHMR_HIP_TRY(kern::launch_verify(a, d_mismatch, rows, 1, 2, stream));
+            continue;
+        }
+        const int u = verify_chunks(rows);
+        const uint64_t tb = kern::tile_bytes(u);
+        const uint64_t full = len / tb;
+        if (full) {
+            a.col_base = 0;
+            a.tiles_per_block = uint32_t(full);
+            a.ntiles = nblocks * full;
+            SHMR_HIP_TRY(kern::launch_verify(a, d_mismatch, rows, u, 0, stream));
+        }
+        if (len % tb) {
+            a.col_base = full * tb;
+            a.tiles_per_block = uint32_t((len - full * tb + tb1 - 1) / tb1);
+            a.ntiles = nblocks * a.tiles_per_block;
+            SHMR_HIP_TRY(kern::launch_verify(a, d_mismatch, rows, 1, 1, stream));
+        }
+    }
+    return SHMR_EC_OK;
 }
 
 int validate_presence(const Codec& c, const uint8_t* present, uint64_t nblocks) {

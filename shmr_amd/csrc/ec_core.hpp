@@ -99,6 +99,7 @@ enum DevCounter {
     kDevCaptureTables,
     kDevCaptureReleased,
     kDevPtrTableGrids,
+    kDevBlocksVerified,
     kDevCounters
 };
 void count_device(int dev, DevCounter c, uint64_t n = 1);
@@ -257,6 +258,17 @@ bool slots_launch_fits(OpClass op, unsigned k, const Layout& L, const uint64_t* 
 // uploaded block list (launch_slots).
 int encode_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint64_t len, hipStream_t stream,
                      const uint64_t* slots = nullptr);
+// Parity check of nblocks blocks laid out per `L` as for encode_on_device
+// (L.out_base: the stored parity, read only): d_mismatch[b] (device memory,
+// 4-byte aligned) is zeroed on `stream`, then bit min(r, 31) is ORed in for
+// every parity row r of block b whose stored bytes differ from the recomputed
+// ones in [0, len).  Stream-ordered; no blocking call after device init.
+int verify_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint64_t len, uint32_t* d_mismatch,
+                     hipStream_t stream);
+// 16-byte chunks per lane of the full-tile verify kernel at `rows` rows:
+// kern::verify_chunks (the tools build: the knob "encode.chunks" = 1 / 2 where
+// set, its measurement).
+int verify_chunks(unsigned rows);
 // The blocks slots[0 .. n) (ascending, distinct) of a single-plan launch set.
 int launch_slots(Plan& plan, int dev, const Layout& L, const uint64_t* slots, uint64_t n, uint64_t len,
                  hipStream_t stream, OpClass op);

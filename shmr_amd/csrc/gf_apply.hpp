@@ -279,6 +279,22 @@ struct KernelInfo {
 };
 size_t kernel_inventory(KernelInfo* out, size_t cap);
 
+// The parity check kernels (gf_verify.hip; ReedSolomon::verify): `a` as for an
+// encode launch of `rows` parity rows from a.row0 (single plan, strided blocks
+// blk_first + j * blk_stride, out_base = the STORED parity, which is only
+// read).  ORs bit min(a.row0 + r, 31) into mismatch[j] for every row r of
+// launch block j whose stored bytes differ from the recomputed ones in this
+// launch's tiles; writes nothing for a block without a difference.  mode 0:
+// full tiles of u = verify_chunks(rows) chunks per lane (the tools build:
+// 1 or 2); mode 1: one
+// partial tail tile per block; mode 2: byte-granular, any alignment.  One
+// workgroup per tile.  Not part of kernel_inventory.
+// The measured tile size (profiles/r07/verify_ab*.jsonl): 8 KiB
+// full tiles (U = 2, wave-contiguous runs) at 3 and 4 rows, +1.4 / +1.7 points
+// of HBM peak over 4 KiB; 1 and 2 rows keep the encode policy's U = 1.
+constexpr int verify_chunks(unsigned rows) { return rows >= 3 ? 2 : 1; }
+hipError_t launch_verify(const ApplyArgs& a, uint32_t* mismatch, unsigned rows, int u, int mode, hipStream_t stream);
+
 // The submission queue's completion mark (submit.cpp): a one-wave kernel on
 // `stream` that stores `seq` to `word` -- pinned host memory, a system-scope
 // release store -- once every earlier kernel of the stream has completed, so

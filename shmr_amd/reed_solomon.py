@@ -191,12 +191,68 @@ class ReedSolomon:
         self._reconstruct(shards, data_only=True)
 
     def verify(self, shards: Sequence) -> bool:
-        """``ReedSolomon::verify``: recompute parity on the GPU and compare."""
-        k = self.data_shard_count()
+        """``ReedSolomon::verify``: whether shards[k:] are the parity of
+        shards[:k] (``shmr_ec_verify``: recomputed and compared on the GPU; no
+        shard is written)."""
         arrs = [_writable_u8(s) if not isinstance(s, (bytes,)) else np.frombuffer(s, np.uint8) for s in shards]
-        tmp = [a.copy() for a in arrs[:k]] + [np.zeros_like(a) for a in arrs[k:]]
-        self.encode(tmp)
-        return all(np.array_equal(a, b) for a, b in zip(tmp[k:], arrs[k:]))
+        n = len(arrs)
+        ptrs = (_u8p * max(n, 1))(*[_ptr(a) for a in arrs])
+        lens = (ctypes.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        ok = ctypes.c_int(0)
+        _check(self._L.shmr_ec_verify(self._h, ptrs, lens, n, ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def verify_batch_dev(self, data, parity, shard_len: Optional[int] = None,
+                         data_shard_pitch: Optional[int] = None, parity_shard_pitch: Optional[int] = None,
+                         device: Optional[int] = None, out=None):
+        """``ReedSolomon::verify`` of a device-resident batch
+        (``shmr_ec_verify_batch_dev``): data and parity as ``encode_batch_dev``
+        takes them (same tensor forms, same bounds checks), parity being the
+        STORED parity, which is only read.
+
+        Returns a ``torch.int32`` tensor ``[B]`` on the tensors' device holding
+        the bit pattern of the mismatch words: 0 = block b is a codeword, else
+        bit min(r, 31) is set for every parity row r whose stored bytes differ
+        from the recomputed ones in [0, shard_len).  ``out``: a contiguous int32
+        ``[B]`` tensor on that device to (over)write instead of a fresh one --
+        e.g. the static result buffer of a captured graph.  Enqueued on torch's
+        current stream; nothing else is written."""
+        import torch
+        B = data.shape[0]
+        dbp = data.stride(0)
+        pbp = parity.stride(0)
+        dsp = data_shard_pitch if data_shard_pitch is not None else (data.stride(1) if data.dim() == 3 else dbp // self.data_shard_count())
+        psp = parity_shard_pitch if parity_shard_pitch is not None else (parity.stride(1) if parity.dim() == 3 else pbp // self.parity_shard_count())
+        L = shard_len if shard_len is not None else dsp
+        if parity.shape[0] != B:
+            raise ValueError(f"data has {B} blocks, parity {parity.shape[0]}")
+        self._check_batch_tensor(data, self.data_shard_count(), dsp, L)
+        self._check_batch_tensor(parity, self.parity_shard_count(), psp, L)
+        self._check_addressable(data, parity)
+        if not data.is_cuda:
+            raise TypeError("verify_batch_dev takes tensors on the GPU")
+        if out is None:
+            out = torch.empty(B, dtype=torch.int32, device=data.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.device != data.device
+              or out.dim() != 1 or out.shape[0] != B or not out.is_contiguous()):
+            raise TypeError(f"out must be a contiguous torch.int32 [{B}] tensor on {data.device}")
+        dev, stream = self._stream_and_device(data)
+        dev = dev if device is None else int(device)
+        _check(self._L.shmr_ec_verify_batch_dev(self._h, ctypes.c_void_p(data.data_ptr()), dsp, dbp,
+                                                ctypes.c_void_p(parity.data_ptr()), psp, pbp, B, L,
+                                                ctypes.c_void_p(out.data_ptr()), dev, stream))
+        return out
+
+    def verify_shards_dev(self, shards, shard_len: Optional[int] = None, device: Optional[int] = None, out=None):
+        """``verify_batch_dev`` of one ``[B, k + p, pitch]`` tensor holding every
+        shard of a block side by side (the layout ``reconstruct_batch_dev``
+        takes), split into its data and parity regions."""
+        if shards.dim() != 3:
+            raise TypeError("shards must be a [blocks, total, bytes] tensor")
+        k, t = self.data_shard_count(), self.total_shard_count()
+        if shards.shape[1] != t:
+            raise Error(-1 if shards.shape[1] < t else -2)       # TooFewShards / TooManyShards
+        return self.verify_batch_dev(shards[:, :k], shards[:, k:], shard_len=shard_len, device=device, out=out)
 
     # -- device-resident batches (torch tensors on the GPU) ------------------------
     @staticmethod
@@ -732,7 +788,7 @@ def path_stats():
 
 DEVICE_COUNTERS = ("blocks_encoded", "blocks_reconstructed", "launches", "plan_images", "upload_rings",
                    "staging_streams", "blocking_calls", "ptr_table_hits", "capture_tables", "capture_released",
-                   "ptr_table_grids")
+                   "ptr_table_grids", "blocks_verified")
 
 
 def device_init(device: int = 0) -> None:
