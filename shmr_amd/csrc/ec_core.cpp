@@ -8,6 +8,8 @@
 #include <unordered_map>
 #include <unordered_set>
 
+#include "run_split.hpp"
+
 namespace shmr {
 namespace core {
 
@@ -426,14 +428,8 @@ bool ptrs_grid() { return g_ptrs_grid.load() != 0; }
 
 bool slots_launch_fits(OpClass op, unsigned k, const Layout& L, const uint64_t* slots, uint64_t n) {
     if (g_lattice_list.load(std::memory_order_relaxed)) return true;
-    uint64_t runs = 0;
-    for (uint64_t i = 0; i < n;) {   // (launch_slots' run split)
-        uint64_t e = i + 1;
-        const uint64_t st = e < n ? slots[e] - slots[i] : 1;
-        while (e < n && slots[e] - slots[e - 1] == st) ++e;
-        if (++runs > kern::kMaxSegs) return false;
-        i = e;
-    }
+    const size_t runs = grid::split_runs(slots, n, nullptr, kern::kMaxSegs, nullptr);
+    if (runs > kern::kMaxSegs) return false;
     return runs <= 1 || segs_supported(op, k, L.host_mapped, L.d_ptrs != nullptr, L.compact);
 }
 
@@ -977,6 +973,65 @@ int plan_on_device(Plan& plan, int dev, hipStream_t stream, bool compact, const 
 // realigning kernel for full 4 KiB tiles plus the byte-granular one for the
 // rest; misaligned mapped host shards take the byte-granular kernel.
 // ===========================================================================
+namespace {
+bool out_aligned16(const Layout& L) {
+    return aligned16(uintptr_t(L.out_base)) && aligned16(L.out_bpitch) && aligned16(L.out_spitch);
+}
+
+// Every address a launch over `L` touches is 16-byte aligned.
+bool layout_aligned16(const Layout& L) {
+    if (L.d_ptrs) return L.ptrs_aligned;
+    return aligned16(uintptr_t(L.in_base)) && aligned16(L.in_bpitch) && aligned16(L.in_spitch) && out_aligned16(L);
+}
+
+// The layout and plan fields of a launch; its blocks, rows and tiles are the caller's.
+kern::ApplyArgs apply_args(const Layout& L, const Plan& plan, const uint8_t* dplan, uint64_t len) {
+    kern::ApplyArgs a{};
+    a.in_base = L.in_base;
+    a.out_base = L.out_base;
+    a.in_bpitch = L.in_bpitch;
+    a.in_spitch = L.in_spitch;
+    a.out_bpitch = L.out_bpitch;
+    a.out_spitch = L.out_spitch;
+    a.out_bias = L.out_bias;
+    a.shard_ptrs = L.d_ptrs;
+    a.total = L.total;
+    a.len = len;
+    a.k = plan.k;
+    a.m = plan.m;
+    a.plan = dplan;
+    a.tab_off = plan_tab_off(plan.k, plan.m);
+    return a;
+}
+
+// The bytes [col0, col1) of every block of the launch, in tiles of tb bytes.
+void set_tiles(kern::ApplyArgs& a, uint64_t col0, uint64_t col1, uint64_t tb) {
+    a.col_base = col0;
+    a.tiles_per_block = uint32_t((col1 - col0 + tb - 1) / tb);
+    a.ntiles = a.nblk * a.tiles_per_block;
+}
+
+// One row group over [0, len) of every block: the full tiles of tb bytes in
+// kernel mode full_mode (0, or 3: realigning loads; -1: none), the rest in
+// 4 KiB tiles with byte-exact bounds in rest_mode (1 behind mode 0, 2 byte-
+// granular; -1: none, the full-tile launch carries the tails).  launch(mode)
+// enqueues `a`.
+template <class Launch>
+int launch_split(kern::ApplyArgs& a, uint64_t len, uint64_t tb, int full_mode, int rest_mode, Launch launch) {
+    const uint64_t cut = full_mode < 0 ? 0 : len / tb * tb;
+    if (cut) {
+        set_tiles(a, 0, cut, tb);
+        const int rc = launch(full_mode);
+        if (rc) return rc;
+    }
+    if (cut < len && rest_mode >= 0) {
+        set_tiles(a, cut, len, kern::tile_bytes(1));
+        return launch(rest_mode);
+    }
+    return SHMR_EC_OK;
+}
+}  // namespace
+
 int launch_set(Plan& plan, int dev, const Layout& L, const BlockSet& bs, uint64_t len, hipStream_t stream,
                OpClass op) {
     const uint64_t nblk = bs.n;
@@ -984,7 +1039,6 @@ int launch_set(Plan& plan, int dev, const Layout& L, const BlockSet& bs, uint64_
     int rc = device_init(dev, stream);
     if (rc) return rc;
     const uint8_t* dplan = nullptr;
-    const uint32_t tab_off = plan_tab_off(plan.k, plan.m);
     if (!bs.d_plans && !bs.segs) {
         rc = plan_on_device(plan, dev, stream, L.compact, &dplan);
         if (rc) return rc;
@@ -1002,11 +1056,19 @@ int launch_set(Plan& plan, int dev, const Layout& L, const BlockSet& bs, uint64_
     // else the realigning kernel below (pitch layouts; misaligned device
     // shard-pointer tables then take the byte-granular kernel).  Mapped host
     // shards never do: the probe covered device memory only.
-    const bool out16 = aligned16(uintptr_t(L.out_base)) && aligned16(L.out_bpitch) && aligned16(L.out_spitch);
-    const bool aligned16_all =
-        ptrs ? L.ptrs_aligned
-             : aligned16(uintptr_t(L.in_base)) && aligned16(L.in_bpitch) && aligned16(L.in_spitch) && out16;
+    const bool out16 = out_aligned16(L);
+    const bool aligned16_all = layout_aligned16(L);
     const bool aligned = aligned16_all || (!L.host_mapped && unaligned_vector(dev));
+    kern::ApplyArgs a = apply_args(L, plan, dplan, len);
+    a.blk_list = bs.d_list;
+    a.blk_first = bs.first;
+    a.blk_stride = bs.stride;
+    a.nblk = nblk;
+    a.plan_table = bs.d_plans;
+    a.blk_plan = bs.d_plan_idx;
+    a.in_identity = (bs.d_plans || bs.segs) ? 0u : uint32_t(identity);
+    a.nseg = bs.segs ? bs.nseg : 0;
+    for (uint32_t i = 0; i < a.nseg; ++i) a.segs[i] = bs.segs[i];
     for (uint32_t row0 = 0; row0 < plan.m; row0 += kern::kMaxRowsPerLaunch) {
         const uint32_t rows = std::min<uint32_t>(kern::kMaxRowsPerLaunch, plan.m - row0);
         count_device(dev, kDevLaunches);
@@ -1039,138 +1101,62 @@ int launch_set(Plan& plan, int dev, const Layout& L, const BlockSet& bs, uint64_
             if (op == kDecode) var.early = false;   // measured (and compiled) on the plain rebuild tile
         }
         const uint64_t tb = kern::tile_bytes(var.u, var.threads);
-        kern::ApplyArgs a{};
-        a.in_base = L.in_base;
-        a.out_base = L.out_base;
-        a.in_bpitch = L.in_bpitch;
-        a.in_spitch = L.in_spitch;
-        a.out_bpitch = L.out_bpitch;
-        a.out_spitch = L.out_spitch;
-        a.out_bias = L.out_bias;
-        a.blk_list = bs.d_list;
-        a.blk_first = bs.first;
-        a.blk_stride = bs.stride;
-        a.nblk = nblk;
-        a.plan_table = bs.d_plans;
-        a.blk_plan = bs.d_plan_idx;
-        a.len = len;
-        a.k = plan.k;
-        a.m = plan.m;
         a.row0 = row0;
-        a.plan = dplan;
-        a.tab_off = tab_off;
-        a.in_identity = (bs.d_plans || bs.segs) ? 0u : uint32_t(identity);
-        a.nseg = bs.segs ? bs.nseg : 0;
-        for (uint32_t i = 0; i < a.nseg; ++i) a.segs[i] = bs.segs[i];
-        a.shard_ptrs = L.d_ptrs;
-        a.total = L.total;
-        if (!aligned) {
-            // Device-resident shards off 16-byte alignment (the reference's
-            // contiguous block buffer, shard i at i * S): full 4 KiB tiles in
-            // the realigning vector kernel (mode 3), the rest byte-granular.
-            // Mapped host shards stay byte-granular: their loads cross PCIe,
-            // where mode 3's second (overlapping) load would be paid again.
-            const uint64_t tb1 = kern::tile_bytes(1);
-            const uint64_t full1 = (ptrs || L.host_mapped) ? 0 : len / tb1;
-            if (full1) {
-                a.col_base = 0;
-                a.tiles_per_block = uint32_t(full1);
-                a.ntiles = nblk * full1;
-                SHMR_HIP_TRY(kern::launch_apply(a, rows, tail, 3, cap, stream));
-            }
-            if (len > full1 * tb1) {
-                a.col_base = full1 * tb1;
-                a.tiles_per_block = uint32_t((len - full1 * tb1 + tb1 - 1) / tb1);
-                a.ntiles = nblk * a.tiles_per_block;
-                SHMR_HIP_TRY(kern::launch_apply(a, rows, tail, 2, cap, stream));
-            }
-            continue;
-        }
-        const uint64_t full = len / tb;
-        const bool fused = var.fuse_tail && full > 0 && len % tb != 0;
+        const bool fused = aligned && var.fuse_tail && len >= tb && len % tb != 0;
         var.fuse_tail = fused;
-        if (full) {
-            a.col_base = 0;
-            a.tiles_per_block = uint32_t(full);
-            a.lead_tails = fused ? nblk : 0;
-            a.ntiles = nblk * full + a.lead_tails;
-            const hipError_t e = kern::launch_apply(a, rows, var, 0, cap, stream);
-            if (e == hipErrorInvalidValue) return SHMR_EC_INVALID_ARGUMENT;   // variant not compiled
-            if (e != hipSuccess) return SHMR_EC_DEVICE_ERROR;
+        auto launch = [&](int mode) -> int {
+            if (mode == 0 && fused) {   // the partial last tile of every block leads the grid
+                a.lead_tails = nblk;
+                a.ntiles += nblk;
+            }
+            const hipError_t e = kern::launch_apply(a, rows, mode == 0 ? var : tail, mode, cap, stream);
             a.lead_tails = 0;
-        }
-        if (len % tb && !fused) {
-            const uint64_t tb1 = kern::tile_bytes(1);
-            a.col_base = full * tb;
-            a.tiles_per_block = uint32_t((len - full * tb + tb1 - 1) / tb1);
-            a.ntiles = nblk * a.tiles_per_block;
-            SHMR_HIP_TRY(kern::launch_apply(a, rows, tail, 1, cap, stream));
-        }
+            if (mode == 0 && e == hipErrorInvalidValue) return SHMR_EC_INVALID_ARGUMENT;   // variant not compiled
+            return e == hipSuccess ? SHMR_EC_OK : SHMR_EC_DEVICE_ERROR;
+        };
+        // Device-resident shards off 16-byte alignment on a device without
+        // unaligned vector access (the reference's contiguous block buffer,
+        // shard i at i * S): full 4 KiB tiles in the realigning vector kernel
+        // (mode 3), the rest byte-granular.  Mapped host shards stay byte-
+        // granular: their loads cross PCIe, where mode 3's second
+        // (overlapping) load would be paid again.
+        rc = aligned ? launch_split(a, len, tb, 0, fused ? -1 : 1, launch)
+                     : launch_split(a, len, kern::tile_bytes(1), (ptrs || L.host_mapped) ? -1 : 3, 2, launch);
+        if (rc) return rc;
     }
     return SHMR_EC_OK;
 }
 
 namespace {
-// A launch's table in device memory: inside a capture a block of the capture
-// reserve (every replay re-reads it; returned when the graph is destroyed),
-// else a slot of the device's table ring, released behind the launch.
-// fill(host) writes the bytes; launch(device copy) enqueues the kernels.
-template <class Fill, class Launch>
-int with_table(int dev, hipStream_t stream, size_t bytes, Fill fill, Launch launch) {
-    bool capturing = false;
-    int rc = capture_state(stream, &capturing);
-    if (rc) return rc;
-    uint8_t *h = nullptr, *d = nullptr;
-    if (capturing) {
-        rc = capture_alloc(dev, stream, bytes, &h, &d);
+// Segment launches of `runs`, run i under device plan dplan_of(i) (nullptr: *rc is set).
+template <class PlanOf>
+int launch_runs(Plan& shape, int dev, const Layout& L, const std::vector<grid::Run>& runs, uint64_t n, uint64_t len,
+                hipStream_t stream, OpClass op, PlanOf dplan_of) {
+    std::vector<kern::Seg> segs(runs.size());
+    for (size_t i = 0; i < runs.size(); ++i) {
+        int rc = SHMR_EC_OK;
+        const uint8_t* dp = dplan_of(runs[i], &rc);
         if (rc) return rc;
-        fill(h);
-        if (hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return SHMR_EC_DEVICE_ERROR;
-        }
-        return launch(d);
+        segs[i] = kern::Seg{uint32_t(runs[i].start), uint32_t(runs[i].first), uint32_t(runs[i].stride), 0, dp};
     }
-    if (bytes > UploadRing::kSlotBytes) return SHMR_EC_INVALID_ARGUMENT;
-    UploadRing* ring = UploadRing::for_device(dev, &rc);
-    if (!ring) return rc;
-    int slot = -1;
-    rc = ring->acquire(&h, &d, &slot);
-    if (rc) return rc;
-    fill(h);
-    rc = ring->upload(slot, bytes, stream);
-    if (rc == SHMR_EC_OK) rc = launch(d);
-    const int rc2 = ring->release_after(slot, stream);
-    return rc ? rc : rc2;
+    BlockSet bs;
+    bs.n = n;
+    bs.segs = segs.data();
+    bs.nseg = uint32_t(segs.size());
+    return launch_set(shape, dev, L, bs, len, stream, op);
 }
 }  // namespace
 
 int launch_slots(Plan& plan, int dev, const Layout& L, const uint64_t* slots, uint64_t n, uint64_t len,
                  hipStream_t stream, OpClass op) {
     if (n == 0) return SHMR_EC_OK;
-    // maximal arithmetic runs of the (ascending) slots
-    std::vector<kern::Seg> segs;
-    bool fits = true;
-    for (uint64_t i = 0; i < n;) {
-        uint64_t e = i + 1;
-        const uint64_t st = e < n ? slots[e] - slots[i] : 1;
-        while (e < n && slots[e] - slots[e - 1] == st) ++e;
-        if (segs.size() == kern::kMaxSegs) {
-            fits = false;
-            break;
-        }
-        kern::Seg sg{};
-        sg.start = uint32_t(i);
-        sg.first = uint32_t(slots[i]);
-        sg.stride = e - i > 1 ? uint32_t(st) : 1u;
-        segs.push_back(sg);
-        i = e;
-    }
+    std::vector<grid::Run> runs;
+    bool fits = grid::split_runs(slots, n, nullptr, kern::kMaxSegs, &runs) <= kern::kMaxSegs;
     if (g_slots_list.load(std::memory_order_relaxed)) fits = false;   // (tools: the list, measured)
-    if (fits && segs.size() == 1) {   // one run: the plain strided launch
+    if (fits && runs.size() == 1) {   // one run: the plain strided launch
         BlockSet bs;
         bs.first = slots[0];
-        bs.stride = segs[0].stride;
+        bs.stride = runs[0].stride;
         bs.n = n;
         return launch_set(plan, dev, L, bs, len, stream, op);
     }
@@ -1180,12 +1166,7 @@ int launch_slots(Plan& plan, int dev, const Layout& L, const uint64_t* slots, ui
         if (rc) return rc;
         rc = plan_on_device(plan, dev, stream, L.compact, &dp);
         if (rc) return rc;
-        for (auto& sg : segs) sg.plan = dp;
-        BlockSet bs;
-        bs.n = n;
-        bs.segs = segs.data();
-        bs.nseg = uint32_t(segs.size());
-        return launch_set(plan, dev, L, bs, len, stream, op);
+        return launch_runs(plan, dev, L, runs, n, len, stream, op, [&](const grid::Run&, int*) { return dp; });
     }
     // an uploaded block list, a ring slot per chunk
     const uint64_t per = UploadRing::kSlotBytes / sizeof(uint32_t);
@@ -1225,7 +1206,7 @@ int encode_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
 // Parity check (ReedSolomon::verify).  The encode plan over the encode layout,
 // L.out_base being the stored parity: per group of <= 4 parity rows one
 // full-tile launch plus, when len is not a multiple of the tile, one launch
-// over the partial last tile -- split as launch_set splits an encode, without
+// over the partial last tile -- launch_split, as an encode's launch_set, without
 // its fused-tail and segment forms.  Misaligned shards take the same kernels
 // where the device serves unaligned vector access, else the byte-granular one.
 // ===========================================================================
@@ -1241,53 +1222,22 @@ int verify_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
     rc = plan_on_device(plan, dev, stream, false, &dplan);
     if (rc) return rc;
     count_device(dev, kDevBlocksVerified, nblocks);
-    const bool aligned16_all = aligned16(uintptr_t(L.in_base)) && aligned16(L.in_bpitch) && aligned16(L.in_spitch) &&
-                               aligned16(uintptr_t(L.out_base)) && aligned16(L.out_bpitch) && aligned16(L.out_spitch);
-    const bool aligned = aligned16_all || unaligned_vector(dev);
-    kern::ApplyArgs a{};
-    a.in_base = L.in_base;
-    a.out_base = L.out_base;
-    a.in_bpitch = L.in_bpitch;
-    a.in_spitch = L.in_spitch;
-    a.out_bpitch = L.out_bpitch;
-    a.out_spitch = L.out_spitch;
-    a.out_bias = L.out_bias;
+    const bool aligned = layout_aligned16(L) || unaligned_vector(dev);
+    kern::ApplyArgs a = apply_args(L, plan, dplan, len);
     a.blk_first = 0;
     a.blk_stride = 1;
     a.nblk = nblocks;
-    a.len = len;
-    a.k = plan.k;
-    a.m = plan.m;
-    a.plan = dplan;
-    a.tab_off = plan_tab_off(plan.k, plan.m);
     a.in_identity = 1;
-    const uint64_t tb1 = kern::tile_bytes(1);
     for (uint32_t row0 = 0; row0 < plan.m; row0 += kern::kMaxRowsPerLaunch) {
         const uint32_t rows = std::min<uint32_t>(kern::kMaxRowsPerLaunch, plan.m - row0);
         count_device(dev, kDevLaunches);
         a.row0 = row0;
-        if (!aligned) {
-            a.col_base = 0;
-            a.tiles_per_block = uint32_t((len + tb1 - 1) / tb1);
-            a.ntiles = nblocks * a.tiles_per_block;
-            SHMR_HIP_TRY(kern::launch_verify(a, d_mismatch, rows, 1, 2, stream));
-            continue;
-        }
-        const int u = verify_chunks(rows);
-        const uint64_t tb = kern::tile_bytes(u);
-        const uint64_t full = len / tb;
-        if (full) {
-            a.col_base = 0;
-            a.tiles_per_block = uint32_t(full);
-            a.ntiles = nblocks * full;
-            SHMR_HIP_TRY(kern::launch_verify(a, d_mismatch, rows, u, 0, stream));
-        }
-        if (len % tb) {
-            a.col_base = full * tb;
-            a.tiles_per_block = uint32_t((len - full * tb + tb1 - 1) / tb1);
-            a.ntiles = nblocks * a.tiles_per_block;
-            SHMR_HIP_TRY(kern::launch_verify(a, d_mismatch, rows, 1, 1, stream));
-        }
+        const int u = aligned ? verify_chunks(rows) : 1;   // the byte-granular kernel (mode 2): 4 KiB tiles
+        rc = launch_split(a, len, kern::tile_bytes(u), aligned ? 0 : -1, aligned ? 1 : 2, [&](int mode) -> int {
+            SHMR_HIP_TRY(kern::launch_verify(a, d_mismatch, rows, mode == 0 ? u : 1, mode, stream));
+            return SHMR_EC_OK;
+        });
+        if (rc) return rc;
     }
     return SHMR_EC_OK;
 }
@@ -1368,42 +1318,19 @@ int reconstruct_on_device(Codec& c, int dev, const Layout& L, const uint8_t* pre
         // travel in the kernel arguments -- no table upload on the stream and
         // no dependent table loads in the kernel prologue.
         {
-            std::vector<kern::Seg> segs;
+            std::vector<grid::Run> runs;
             // (device shard-pointer tables: knob "ptrs_segs")
-            bool fits = (!(L.d_ptrs && !L.host_mapped) || g_ptrs_segs.load() != 0) &&
-                        segs_supported(kDecode, c.k(), L.host_mapped, L.d_ptrs != nullptr, L.compact);
-            for (size_t i = 0; i < grp.blocks.size() && fits;) {
-                size_t e = i + 1;
-                const uint32_t st = e < grp.blocks.size() ? grp.blocks[e] - grp.blocks[i] : 1;
-                while (e < grp.blocks.size() && grp.plan_idx[e] == grp.plan_idx[i] &&
-                       grp.blocks[e] > grp.blocks[e - 1] && grp.blocks[e] - grp.blocks[e - 1] == st)
-                    ++e;
-                if (segs.size() == kern::kMaxSegs) {
-                    fits = false;
-                    break;
-                }
-                kern::Seg sg{};
-                sg.start = uint32_t(i);
-                sg.first = grp.blocks[i];
-                sg.stride = e - i > 1 ? st : 1;
-                segs.push_back(sg);
-                // remember the plan index in pad_ until the device pointers are known
-                segs.back().pad_ = grp.plan_idx[i];
-                i = e;
-            }
+            const bool fits = (!(L.d_ptrs && !L.host_mapped) || g_ptrs_segs.load() != 0) &&
+                              segs_supported(kDecode, c.k(), L.host_mapped, L.d_ptrs != nullptr, L.compact) &&
+                              grid::split_runs(grp.blocks.data(), grp.blocks.size(), grp.plan_idx.data(),
+                                               kern::kMaxSegs, &runs) <= kern::kMaxSegs;
             if (fits) {
-                for (auto& sg : segs) {
-                    const uint8_t* dp = nullptr;
-                    rc = plan_on_device(*grp.plans[sg.pad_], dev, stream, L.compact, &dp);
-                    if (rc) return rc;
-                    sg.plan = dp;
-                    sg.pad_ = 0;
-                }
-                BlockSet bs;
-                bs.n = grp.blocks.size();
-                bs.segs = segs.data();
-                bs.nseg = uint32_t(segs.size());
-                rc = launch_set(*grp.plans[0], dev, L, bs, len, stream, kDecode);
+                rc = launch_runs(*grp.plans[0], dev, L, runs, grp.blocks.size(), len, stream, kDecode,
+                                 [&](const grid::Run& r, int* prc) {
+                                     const uint8_t* dp = nullptr;
+                                     *prc = plan_on_device(*grp.plans[r.plan], dev, stream, L.compact, &dp);
+                                     return dp;
+                                 });
                 if (rc) return rc;
                 continue;
             }
@@ -1427,59 +1354,34 @@ int reconstruct_on_device(Codec& c, int dev, const Layout& L, const uint8_t* pre
         bool capturing = false;
         rc = capture_state(stream, &capturing);
         if (rc) return rc;
-        if (capturing) {
-            // Inside a capture the tables must outlive every replay: a block of
-            // the capture reserve, returned when the graph is destroyed.
-            const size_t n = grp.blocks.size();
-            const size_t list_off = ptab_bytes;
-            const size_t pidx_off = (list_off + n * sizeof(uint32_t) + 15) & ~size_t(15);
-            const size_t total = pidx_off + n * sizeof(uint16_t);
-            uint8_t *h = nullptr, *d = nullptr;
-            rc = capture_alloc(dev, stream, total, &h, &d);
-            if (rc) return rc;
-            std::memcpy(h, dplans.data(), dplans.size() * sizeof(void*));
-            std::memcpy(h + list_off, grp.blocks.data(), n * sizeof(uint32_t));
-            std::memcpy(h + pidx_off, grp.plan_idx.data(), n * sizeof(uint16_t));
-            if (hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, stream) != hipSuccess) {
-                (void)hipGetLastError();
-                return SHMR_EC_DEVICE_ERROR;
-            }
-            BlockSet bs;
-            bs.n = n;
-            bs.d_plans = reinterpret_cast<const uint8_t* const*>(d);
-            bs.d_list = reinterpret_cast<const uint32_t*>(d + list_off);
-            bs.d_plan_idx = reinterpret_cast<const uint16_t*>(d + pidx_off);
-            rc = launch_set(*grp.plans[0], dev, L, bs, len, stream, kDecode);
-            if (rc) return rc;
-            continue;
+        // One table per chunk -- plan pointers, block list, per-block plan
+        // indices.  Inside a capture the whole group in one block of the
+        // capture reserve, else ring slots' worth of blocks at a time.
+        size_t per_chunk = grp.blocks.size();
+        if (!capturing) {
+            if (ptab_bytes + 64 > UploadRing::kSlotBytes) return SHMR_EC_INVALID_ARGUMENT;
+            per_chunk = (UploadRing::kSlotBytes - ptab_bytes - 32) / (sizeof(uint32_t) + sizeof(uint16_t));
         }
-        UploadRing* ring = UploadRing::for_device(dev, &rc);
-        if (!ring) return rc;
-        const size_t table_bytes = ptab_bytes;
-        if (table_bytes + 64 > UploadRing::kSlotBytes) return SHMR_EC_INVALID_ARGUMENT;
-        const size_t per_chunk = (UploadRing::kSlotBytes - table_bytes - 32) / (sizeof(uint32_t) + sizeof(uint16_t));
         for (size_t c0 = 0; c0 < grp.blocks.size(); c0 += per_chunk) {
             const size_t n = std::min(per_chunk, grp.blocks.size() - c0);
-            uint8_t *hslot = nullptr, *dslot = nullptr;
-            int slot = -1;
-            rc = ring->acquire(&hslot, &dslot, &slot);
-            if (rc) return rc;
-            const size_t list_off = table_bytes;
+            const size_t list_off = ptab_bytes;
             const size_t pidx_off = (list_off + n * sizeof(uint32_t) + 15) & ~size_t(15);
-            const size_t total = pidx_off + n * sizeof(uint16_t);
-            std::memcpy(hslot, dplans.data(), dplans.size() * sizeof(void*));
-            std::memcpy(hslot + list_off, grp.blocks.data() + c0, n * sizeof(uint32_t));
-            std::memcpy(hslot + pidx_off, grp.plan_idx.data() + c0, n * sizeof(uint16_t));
-            rc = ring->upload(slot, total, stream);
-            BlockSet bs;
-            bs.n = n;
-            bs.d_plans = reinterpret_cast<const uint8_t* const*>(dslot);
-            bs.d_list = reinterpret_cast<const uint32_t*>(dslot + list_off);
-            bs.d_plan_idx = reinterpret_cast<const uint16_t*>(dslot + pidx_off);
-            if (rc == SHMR_EC_OK) rc = launch_set(*grp.plans[0], dev, L, bs, len, stream, kDecode);
-            const int rc2 = ring->release_after(slot, stream);
+            rc = with_table(
+                dev, stream, pidx_off + n * sizeof(uint16_t),
+                [&](uint8_t* h) {
+                    std::memcpy(h, dplans.data(), dplans.size() * sizeof(void*));
+                    std::memcpy(h + list_off, grp.blocks.data() + c0, n * sizeof(uint32_t));
+                    std::memcpy(h + pidx_off, grp.plan_idx.data() + c0, n * sizeof(uint16_t));
+                },
+                [&](const uint8_t* d) {
+                    BlockSet bs;
+                    bs.n = n;
+                    bs.d_plans = reinterpret_cast<const uint8_t* const*>(d);
+                    bs.d_list = reinterpret_cast<const uint32_t*>(d + list_off);
+                    bs.d_plan_idx = reinterpret_cast<const uint16_t*>(d + pidx_off);
+                    return launch_set(*grp.plans[0], dev, L, bs, len, stream, kDecode);
+                });
             if (rc) return rc;
-            if (rc2) return rc2;
         }
     }
     return SHMR_EC_OK;

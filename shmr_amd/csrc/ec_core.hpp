@@ -337,6 +337,44 @@ private:
     std::condition_variable cv_;
 };
 
+// A launch's table in device memory: inside a capture a block of the capture
+// reserve (every replay re-reads it; returned when the graph is destroyed),
+// else a slot of the device's ring `kind`, released behind the launch (also
+// when the launch failed; its status comes first).  fill(host) writes the
+// bytes; launch(table) enqueues the kernels on the table's device copy -- or,
+// with `direct` outside a capture, on the pinned slot itself, no upload
+// (UploadRing::host_view, where the ring has one).
+template <class Fill, class Launch>
+int with_table(int dev, hipStream_t stream, size_t bytes, Fill fill, Launch launch,
+               UploadRing::Kind kind = UploadRing::kTables, bool direct = false) {
+    bool capturing = false;
+    int rc = capture_state(stream, &capturing);
+    if (rc) return rc;
+    uint8_t *h = nullptr, *d = nullptr;
+    if (capturing) {
+        rc = capture_alloc(dev, stream, bytes, &h, &d);
+        if (rc) return rc;
+        fill(h);
+        if (hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return SHMR_EC_DEVICE_ERROR;
+        }
+        return launch(d);
+    }
+    if (bytes > UploadRing::kSlotBytes) return SHMR_EC_INVALID_ARGUMENT;
+    UploadRing* ring = UploadRing::for_device(dev, &rc, kind);
+    if (!ring) return rc;
+    int slot = -1;
+    rc = ring->acquire(&h, &d, &slot);
+    if (rc) return rc;
+    fill(h);
+    const uint8_t* view = direct ? ring->host_view(slot) : nullptr;
+    if (!view) rc = ring->upload(slot, bytes, stream);
+    if (rc == SHMR_EC_OK) rc = launch(view ? view : d);
+    const int rc2 = ring->release_after(slot, stream);
+    return rc ? rc : rc2;
+}
+
 // Events the library later queries, or makes another stream wait on, from any
 // thread are never used as recorded on a caller's stream: that stream may have
 // begun a graph capture since: a query of an event whose stream is capturing

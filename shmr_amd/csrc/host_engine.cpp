@@ -305,49 +305,40 @@ int run_mapped(const HostJob& job, const std::vector<uint64_t>& dptrs, bool alig
             return;
         }
         const hipStream_t stream = lease.s->stream;
-        UploadRing* ring = UploadRing::for_device(dev, &rc, UploadRing::kPointers);
-        if (!ring) {
-            result = rc;
-            return;
-        }
         const size_t per_chunk = UploadRing::kSlotBytes / (sizeof(uint64_t) * t);
         std::vector<uint8_t> present;
         for (size_t c0 = 0; c0 < mine.size() && rc == SHMR_EC_OK; c0 += per_chunk) {
             const size_t n = std::min(per_chunk, mine.size() - c0);
-            uint8_t *hslot = nullptr, *dslot = nullptr;
-            int slot = -1;
-            rc = ring->acquire(&hslot, &dslot, &slot);
-            if (rc) break;
-            // rows in plan order (kern::ApplyArgs::shard_ptrs): reconstructs permuted per block
-            uint64_t* tab = reinterpret_cast<uint64_t*>(hslot);
-            for (size_t j = 0; j < n; ++j)
-                permute_ptr_rows(dptrs.data() + mine[c0 + j] * t,
-                                 job.op == kEncode ? nullptr : job.present + mine[c0 + j] * t, 1, c.k(), t,
-                                 job.data_only, tab + j * t);
             // small launches (few 4 KiB tiles) read the table from the pinned slot
             // itself: no H2D copy in front of the kernel.  Larger ones upload it --
             // every workgroup reads its block's table, and across PCIe that costs
             // concurrent per-block calls 1-4 % of throughput.
             const uint64_t tiles = n * ((job.len + 4095) / 4096);
-            const uint8_t* direct = tiles <= ptrs_direct_max() ? ring->host_view(slot) : nullptr;
-            if (!direct) rc = ring->upload(slot, n * t * sizeof(uint64_t), stream);
-            Layout L{nullptr, nullptr, 0, 0, 0, 0, 0};
-            L.d_ptrs = reinterpret_cast<const uint64_t*>(direct ? direct : dslot);
-            L.total = t;
-            L.ptrs_aligned = aligned;
-            L.host_mapped = true;
-            if (rc == SHMR_EC_OK) {
-                if (job.op == kEncode) {
-                    rc = encode_on_device(c, dev, L, n, job.len, stream);
-                } else {
+            // (with_table asks the stream for its capture state: a pooled stream
+            // never captures, so that query is all it adds to a ring slot here)
+            rc = with_table(
+                dev, stream, n * t * sizeof(uint64_t),
+                [&](uint8_t* h) {
+                    // rows in plan order (kern::ApplyArgs::shard_ptrs): reconstructs permuted per block
+                    uint64_t* tab = reinterpret_cast<uint64_t*>(h);
+                    for (size_t j = 0; j < n; ++j)
+                        permute_ptr_rows(dptrs.data() + mine[c0 + j] * t,
+                                         job.op == kEncode ? nullptr : job.present + mine[c0 + j] * t, 1, c.k(), t,
+                                         job.data_only, tab + j * t);
+                },
+                [&](const uint8_t* d) {
+                    Layout L{nullptr, nullptr, 0, 0, 0, 0, 0};
+                    L.d_ptrs = reinterpret_cast<const uint64_t*>(d);
+                    L.total = t;
+                    L.ptrs_aligned = aligned;
+                    L.host_mapped = true;
+                    if (job.op == kEncode) return encode_on_device(c, dev, L, n, job.len, stream);
                     present.resize(n * t);
                     for (size_t j = 0; j < n; ++j)
                         std::memcpy(present.data() + j * t, job.present + mine[c0 + j] * t, t);
-                    rc = reconstruct_on_device(c, dev, L, present.data(), n, job.len, job.data_only, stream);
-                }
-            }
-            const int rc2 = ring->release_after(slot, stream);
-            if (rc == SHMR_EC_OK) rc = rc2;
+                    return reconstruct_on_device(c, dev, L, present.data(), n, job.len, job.data_only, stream);
+                },
+                UploadRing::kPointers, tiles <= ptrs_direct_max());
         }
         if (async && rc == SHMR_EC_OK) {   // the caller waits (finish_async)
             *async = lease.s;

@@ -18,6 +18,7 @@
 
 #include "ec_core.hpp"
 #include "ptr_grid.hpp"
+#include "run_split.hpp"
 
 namespace shmr {
 namespace core {
@@ -153,18 +154,9 @@ bool lattice_needs_plan_list(unsigned t, const uint8_t* present, const LatticeFo
     for (const auto& g : by_pattern) {
         unsigned m = 0;
         for (uint8_t x : g.first) m += x ? 0 : 1;
-        size_t runs = 0;
-        const auto& v = g.second;
-        for (size_t i = 0; i < v.size();) {
-            size_t e = i + 1;
-            const uint64_t st = e < v.size() ? v[e] - v[i] : 1;
-            while (e < v.size() && v[e] - v[e - 1] == st) ++e;
-            ++runs;
-            i = e;
-        }
         auto& c = by_m[m];
         c.first += 1;
-        c.second += runs;
+        c.second += grid::split_runs(g.second.data(), g.second.size(), nullptr, kern::kMaxSegs, nullptr);
     }
     for (const auto& kv : by_m)
         if (kv.second.first > 1 && kv.second.second > kern::kMaxSegs) return true;
@@ -232,28 +224,19 @@ int ptrs_launch(Codec& c, const uint64_t* tab, const uint8_t* present, size_t nb
     };
     bool capturing = false;
     if ((rc = capture_state(stream, &capturing))) return rc;
-    if (capturing) {   // a block of the capture reserve, returned when the graph is destroyed
-        const size_t bytes = nblocks * t * sizeof(uint64_t);
-        uint8_t *h = nullptr, *d = nullptr;
-        rc = capture_alloc(device, stream, bytes, &h, &d);
-        if (rc) return rc;
-        std::memcpy(h, table, bytes);
-        if (hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return SHMR_EC_DEVICE_ERROR;
-        }
-        return run(d, 0, nblocks);
-    }
-    PtrTableCache* cache = nullptr;
-    if (use_cache && !host_mapped && !(cache = PtrTableCache::for_device(device, &rc))) return rc;
-    UploadRing* ring = nullptr;
-    const size_t per_chunk = UploadRing::kSlotBytes / (sizeof(uint64_t) * t);
+    PtrTableCache* cache = nullptr;   // (serves no captured call)
+    if (!capturing && use_cache && !host_mapped && !(cache = PtrTableCache::for_device(device, &rc))) return rc;
+    // Inside a capture the whole table in one block of the capture reserve,
+    // else a slot of the pointer ring per chunk of rows.
+    const size_t per_chunk = capturing ? nblocks : UploadRing::kSlotBytes / (sizeof(uint64_t) * t);
     for (size_t b0 = 0; b0 < nblocks; b0 += per_chunk) {
         const size_t n = std::min(per_chunk, nblocks - b0);
+        const uint64_t* rows = table + b0 * t;
+        const size_t bytes = n * t * sizeof(uint64_t);
         if (cache) {   // a table this stream passed before (same bytes): its device copy, no upload
             const uint8_t* dtab = nullptr;
             int entry = -1;
-            rc = cache->lookup(table + b0 * t, n * t * sizeof(uint64_t), stream, &dtab, &entry);
+            rc = cache->lookup(rows, bytes, stream, &dtab, &entry);
             if (rc) return rc;
             if (dtab) {
                 rc = run(dtab, b0, n);
@@ -263,23 +246,16 @@ int ptrs_launch(Codec& c, const uint64_t* tab, const uint8_t* present, size_t nb
                 continue;
             }
         }
-        if (!ring && !(ring = UploadRing::for_device(device, &rc, UploadRing::kPointers))) return rc;
-        uint8_t *hslot = nullptr, *dslot = nullptr;
-        int slot = -1;
-        rc = ring->acquire(&hslot, &dslot, &slot);
-        if (rc) return rc;
-        std::memcpy(hslot, table + b0 * t, n * t * sizeof(uint64_t));
         // Mapped shards: small launches (few 4 KiB tiles) read the table from
         // the pinned slot itself, no H2D copy in front of the kernel (every
         // workgroup reads its block's row; across PCIe that costs larger
         // launches 1-4 %, so they upload it).
         const uint64_t tiles = n * ((len + 4095) / 4096);
-        const uint8_t* direct = host_mapped && tiles <= ptrs_direct_max() ? ring->host_view(slot) : nullptr;
-        rc = direct ? SHMR_EC_OK : ring->upload(slot, n * t * sizeof(uint64_t), stream);
-        if (rc == SHMR_EC_OK) rc = run(direct ? direct : dslot, b0, n);
-        const int rc2 = ring->release_after(slot, stream);
+        rc = with_table(
+            device, stream, bytes, [&](uint8_t* h) { std::memcpy(h, rows, bytes); },
+            [&](const uint8_t* d) { return run(d, b0, n); }, UploadRing::kPointers,
+            host_mapped && tiles <= ptrs_direct_max());
         if (rc) return rc;
-        if (rc2) return rc2;
     }
     return SHMR_EC_OK;
 }
