@@ -228,14 +228,8 @@ int shmr_ec_describe_variant(int decode, uint32_t data_shards, uint32_t rows, ch
                   v.u, int(v.nt_load), int(v.nt_store), int(v.occ8), v.threads,
                   core::grid_mode(op), int(v.diag), v.depth, v.wgs_per_cu, v.occ, int(v.early), int(v.spre), int(v.fuse_tail),
                   int(compiled));
-    // appended only when set: records keyed by the string stay valid
-    for (const auto& kv : {std::make_pair(v.glds, " glds=1"), std::make_pair(v.serial, " serial=1"),
-                           std::make_pair(v.sc1_store, " sc1_store=1"), std::make_pair(v.realign, " realign=1"),
-                           std::make_pair(v.peel, " peel=1"), std::make_pair(v.wave_run, " wave_run=1"),
-                           std::make_pair(v.st_align, " st_align=1"), std::make_pair(v.xcd, " xcd=1"), std::make_pair(v.pair, " pair=1")}) {
-        const size_t n = std::strlen(buf);
-        if (kv.first && n + 1 < len) std::snprintf(buf + n, len - n, "%s", kv.second);
-    }
+    // the later flags are appended only when set: records keyed by the string stay valid
+    core::describe_variant_tail(v, buf, len);
     return SHMR_EC_OK;
 }
 
@@ -535,62 +529,124 @@ int run_req(std::unique_ptr<core::SubmitReq> r, core::SubmitReq** queued) {
     }
     return core::wait(r.get());
 }
+
+// idx[i] = i for i < t: the shard lists of a call that takes shards in index order.
+void identity_idx(uint16_t (&idx)[256], unsigned t) {
+    for (unsigned i = 0; i < t; ++i) idx[i] = uint16_t(i);
+}
+
+// The staged leg of a single-block host call: shards in[0 .. nin) are gathered
+// into pooled device staging (a pitch layout with `extra` bytes behind it; the
+// pool grows without freeing), `run(staging, pitch)` works on it, and shards
+// out[0 .. nout) are copied back.
+template <class Run>
+int run_staged(uint8_t* const* shards, size_t len, unsigned t, int dev, const uint16_t* in, unsigned nin,
+               const uint16_t* out, unsigned nout, size_t extra, Run&& run) {
+    core::DeviceScope scope(dev);
+    if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
+    const uint64_t pitch = core::round_up(len, 256);
+    int rc = SHMR_EC_OK;
+    core::StagingLease lease;
+    lease.s = core::StagingPool::get().acquire(dev, pitch * t + extra, &rc);
+    if (!lease.s) return rc;
+    core::Staging& s = *lease.s;
+    for (unsigned i = 0; i < nin; ++i)
+        SHMR_HIP_TRY(hipMemcpyAsync(s.dbuf + in[i] * pitch, shards[in[i]], len, hipMemcpyHostToDevice, s.stream));
+    rc = run(s, pitch);
+    if (rc) return rc;
+    for (unsigned m = 0; m < nout; ++m)
+        SHMR_HIP_TRY(hipMemcpyAsync(shards[out[m]], s.dbuf + out[m] * pitch, len, hipMemcpyDeviceToHost, s.stream));
+    SHMR_HIP_TRY(core::sync_stream(s.stream));
+    return SHMR_EC_OK;
+}
+
+// One validated block in host buffers (shmr_ec_encode, shmr_ec_reconstruct and
+// their _start forms), by the first leg that applies:
+//  * knob "coalesce" and mapped shards: through the submission queue, merged
+//    with concurrent calls and coded in place;
+//  * mapped shards: coded in place by the kernel (zero-copy);
+//  * pageable and small (bounce_limit): one bounce, one launch;
+//  * else staged: shards in[0 .. k) copied to the device, `run`, shards
+//    out[0 .. nout) copied back.
+// async != nullptr (a _start call): shards in mapped memory are coded by kernels
+// left running (a pooled stream in *async, or a request in *queued); every
+// other leg finishes here.
+template <class Run>
+int host_block(shmr_ec_t* rs, core::OpClass op, bool data_only, uint8_t* const* shards, const uint8_t* present,
+               size_t len, const uint16_t* in, const uint16_t* out, unsigned nout, core::Staging** async,
+               core::SubmitReq** queued, Run&& run) {
+    Codec& c = *rs->codec;
+    const unsigned k = c.k(), t = k + c.p();
+    const int dev = rs->device;
+    int rc = core::check_device(dev);
+    if (rc) return rc;
+    const core::HostJob job{c, op, data_only, shards, present, 1, len, 0, 1};
+    if (core::coalesce_host()) {
+        std::vector<uint64_t> row;
+        if (core::map_rows(job, &row)) {
+            core::count_blocks(true, 1);
+            return run_req(make_req(rs, op, data_only, true, len, dev, std::move(row), present),
+                           async ? queued : nullptr);
+        }
+    }
+    bool handled = false;
+    rc = core::run_mapped_job(job, &dev, 1, &handled, true, async);
+    if (handled || rc) return rc;
+    if (uint64_t(t) * len <= core::bounce_limit()) return core::run_bounced_job(job, dev);
+    core::count_blocks(false, 1);
+    return run_staged(shards, len, t, dev, in, k, out, nout, 0, run);
+}
+
+int arg_ok(bool ok) { return ok ? SHMR_EC_OK : SHMR_EC_INVALID_ARGUMENT; }
+
+// A batch call on device memory, after its checks of rs and the presence flags:
+// an empty batch is done, empty shards are refused, then `check` (the call's own
+// pointers and flags, before any device is asked for), then `launch` with the
+// device selected.
+template <class Check, class Launch>
+int batch_dev(size_t nblocks, size_t shard_len, int device, Check&& check, Launch&& launch) {
+    if (nblocks == 0) return SHMR_EC_OK;
+    if (shard_len == 0) return SHMR_EC_EMPTY_SHARD;
+    int rc = check();
+    if (rc) return rc;
+    rc = core::check_device(device);
+    if (rc) return rc;
+    core::DeviceScope scope(device);
+    if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
+    return launch();
+}
+
+// Every shard a batch call reads or writes has a buffer: all of an encode, and
+// of a reconstruct all but absent parity under data_only.
+bool needed_shards_given(uint8_t* const* shards, const uint8_t* present, size_t nblocks, unsigned k, unsigned t,
+                         bool data_only) {
+    for (size_t b = 0; b < nblocks; ++b)
+        for (unsigned i = 0; i < t; ++i) {
+            const bool needed = !present || present[b * t + i] || i < k || !data_only;
+            if (needed && !shards[b * t + i]) return false;
+        }
+    return true;
+}
 }  // namespace
 
 extern "C" {
 
 // ---- host-buffer encode (ReedSolomon::encode) --------------------------------------
-// async != nullptr (shmr_ec_encode_start): shards in mapped memory are coded by
-// kernels left running (a pooled stream in *async, or -- through the
-// submission queue, knob "coalesce" -- a request in *queued); every other path
-// finishes here.
 static int encode_impl(shmr_ec_t* rs, uint8_t* const* shards, const size_t* shard_lens, size_t nshards,
                        core::Staging** async, core::SubmitReq** queued) {
     return guarded([&]() -> int {
         size_t len = 0;
-        int rc = check_encode(rs, shards, shard_lens, nshards, &len);
+        const int rc = check_encode(rs, shards, shard_lens, nshards, &len);
         if (rc) return rc;
         Codec& c = *rs->codec;
-        const unsigned k = c.k(), p = c.p(), t = k + p;
-        const int dev = rs->device;
-        rc = core::check_device(dev);
-        if (rc) return rc;
-        if (core::coalesce_host()) {   // mapped shards: merged with concurrent calls, coded in place
-            const core::HostJob job{c, core::kEncode, false, shards, nullptr, 1, len, 0, 1};
-            std::vector<uint64_t> row;
-            if (core::map_rows(job, &row)) {
-                core::count_blocks(true, 1);
-                return run_req(make_req(rs, core::kEncode, false, true, len, dev, std::move(row), nullptr),
-                               async ? queued : nullptr);
-            }
-        }
-        {   // shards in mapped memory: the kernel encodes them in place (zero-copy)
-            const core::HostJob job{c, core::kEncode, false, shards, nullptr, 1, len, 0, 1};
-            bool handled = false;
-            rc = core::run_mapped_job(job, &dev, 1, &handled, true, async);
-            if (handled || rc) return rc;
-        }
-        if (uint64_t(t) * len <= core::bounce_limit()) {   // pageable, small: one bounce, one launch
-            const core::HostJob job{c, core::kEncode, false, shards, nullptr, 1, len, 0, 1};
-            return core::run_bounced_job(job, dev);
-        }
-        core::count_blocks(false, 1);
-        core::DeviceScope scope(dev);
-        if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
-        const uint64_t pitch = core::round_up(len, 256);
-        core::StagingLease lease;
-        lease.s = core::StagingPool::get().acquire(dev, pitch * t, &rc);
-        if (!lease.s) return rc;
-        core::Staging& s = *lease.s;
-        for (unsigned i = 0; i < k; ++i)
-            SHMR_HIP_TRY(hipMemcpyAsync(s.dbuf + i * pitch, shards[i], len, hipMemcpyHostToDevice, s.stream));
-        const core::Layout L{s.dbuf, s.dbuf, 0, pitch, 0, pitch, 0};
-        rc = core::encode_on_device(c, dev, L, 1, len, s.stream);
-        if (rc) return rc;
-        for (unsigned r = 0; r < p; ++r)
-            SHMR_HIP_TRY(hipMemcpyAsync(shards[k + r], s.dbuf + (k + r) * pitch, len, hipMemcpyDeviceToHost, s.stream));
-        SHMR_HIP_TRY(core::sync_stream(s.stream));
-        return SHMR_EC_OK;
+        const unsigned k = c.k(), p = c.p();
+        uint16_t idx[256];
+        identity_idx(idx, k + p);
+        return host_block(rs, core::kEncode, false, shards, nullptr, len, idx, idx + k, p, async, queued,
+                          [&](core::Staging& s, uint64_t pitch) {
+                              const core::Layout L{s.dbuf, s.dbuf, 0, pitch, 0, pitch, 0};
+                              return core::encode_on_device(c, rs->device, L, 1, len, s.stream);
+                          });
     });
 }
 
@@ -600,52 +656,15 @@ static int reconstruct_impl(shmr_ec_t* rs, uint8_t* const* shards, const size_t*
     return guarded([&]() -> int {
         size_t len = 0;
         std::shared_ptr<Plan> plan;
-        int rc = check_reconstruct(rs, shards, shard_lens, present, nshards, data_only, &len, &plan);
+        const int rc = check_reconstruct(rs, shards, shard_lens, present, nshards, data_only, &len, &plan);
         if (rc || !plan) return rc;
         Codec& c = *rs->codec;
-        const unsigned k = c.k(), t = k + c.p();
-        const int dev = rs->device;
-        rc = core::check_device(dev);
-        if (rc) return rc;
-        if (core::coalesce_host()) {   // mapped shards: merged with concurrent calls, rebuilt in place
-            const core::HostJob job{c, core::kDecode, data_only != 0, shards, present, 1, len, 0, 1};
-            std::vector<uint64_t> row;
-            if (core::map_rows(job, &row)) {
-                core::count_blocks(true, 1);
-                return run_req(make_req(rs, core::kDecode, data_only != 0, true, len, dev, std::move(row), present),
-                               async ? queued : nullptr);
-            }
-        }
-        {   // shards in mapped memory: rebuilt in place by the kernel (zero-copy)
-            const core::HostJob job{c, core::kDecode, data_only != 0, shards, present, 1, len, 0, 1};
-            bool handled = false;
-            rc = core::run_mapped_job(job, &dev, 1, &handled, true, async);
-            if (handled || rc) return rc;
-        }
-        if (uint64_t(t) * len <= core::bounce_limit()) {   // pageable, small: one bounce, one launch
-            const core::HostJob job{c, core::kDecode, data_only != 0, shards, present, 1, len, 0, 1};
-            return core::run_bounced_job(job, dev);
-        }
-        core::count_blocks(false, 1);
-        core::DeviceScope scope(dev);
-        if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
-        const uint64_t pitch = core::round_up(len, 256);
-        core::StagingLease lease;
-        lease.s = core::StagingPool::get().acquire(dev, pitch * t, &rc);
-        if (!lease.s) return rc;
-        core::Staging& s = *lease.s;
-        for (unsigned i = 0; i < k; ++i) {
-            const unsigned idx = plan->in_idx[i];
-            SHMR_HIP_TRY(hipMemcpyAsync(s.dbuf + idx * pitch, shards[idx], len, hipMemcpyHostToDevice, s.stream));
-        }
-        rc = core::reconstruct_on_device(c, dev, s.dbuf, pitch, pitch * t, present, 1, len, data_only != 0, s.stream);
-        if (rc) return rc;
-        for (unsigned m = 0; m < plan->m; ++m) {
-            const unsigned idx = plan->out_idx[m];
-            SHMR_HIP_TRY(hipMemcpyAsync(shards[idx], s.dbuf + idx * pitch, len, hipMemcpyDeviceToHost, s.stream));
-        }
-        SHMR_HIP_TRY(core::sync_stream(s.stream));
-        return SHMR_EC_OK;
+        const unsigned t = c.k() + c.p();
+        return host_block(rs, core::kDecode, data_only != 0, shards, present, len, plan->in_idx.data(),
+                          plan->out_idx.data(), plan->m, async, queued, [&](core::Staging& s, uint64_t pitch) {
+                              return core::reconstruct_on_device(c, rs->device, s.dbuf, pitch, pitch * t, present, 1,
+                                                                 len, data_only != 0, s.stream);
+                          });
     });
 }
 
@@ -692,9 +711,8 @@ int shmr_ec_reconstruct(shmr_ec_t* rs, uint8_t* const* shards, const size_t* sha
 }
 
 // ---- host-buffer verify (ReedSolomon::verify) ---------------------------------------
-// The block is gathered into pooled device staging (a pitch layout; the pool
-// grows without freeing) with the result word behind it, checked by the batch
-// kernels, and the word copied back.
+// The staged leg over every shard, with the result word behind the block:
+// checked by the batch kernels, and the word copied back.
 int shmr_ec_verify(shmr_ec_t* rs, uint8_t* const* shards, const size_t* shard_lens, size_t nshards,
                    int* consistent) {
     return guarded([&]() -> int {
@@ -707,22 +725,18 @@ int shmr_ec_verify(shmr_ec_t* rs, uint8_t* const* shards, const size_t* shard_le
         const int dev = rs->device;
         rc = core::check_device(dev);
         if (rc) return rc;
-        core::DeviceScope scope(dev);
-        if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
-        const uint64_t pitch = core::round_up(len, 256);
-        core::StagingLease lease;
-        lease.s = core::StagingPool::get().acquire(dev, pitch * t + 256, &rc);
-        if (!lease.s) return rc;
-        core::Staging& s = *lease.s;
-        for (unsigned i = 0; i < t; ++i)
-            SHMR_HIP_TRY(hipMemcpyAsync(s.dbuf + i * pitch, shards[i], len, hipMemcpyHostToDevice, s.stream));
-        uint32_t* d_word = reinterpret_cast<uint32_t*>(s.dbuf + pitch * t);
-        const core::Layout L{s.dbuf, s.dbuf + k * pitch, 0, pitch, 0, pitch, k};
-        rc = core::verify_on_device(c, dev, L, 1, len, d_word, s.stream);
-        if (rc) return rc;
+        uint16_t idx[256];
+        identity_idx(idx, t);
         uint32_t word = 0;
-        SHMR_HIP_TRY(hipMemcpyAsync(&word, d_word, sizeof(word), hipMemcpyDeviceToHost, s.stream));
-        SHMR_HIP_TRY(core::sync_stream(s.stream));
+        rc = run_staged(shards, len, t, dev, idx, t, nullptr, 0, 256, [&](core::Staging& s, uint64_t pitch) -> int {
+            uint32_t* d_word = reinterpret_cast<uint32_t*>(s.dbuf + pitch * t);
+            const core::Layout L{s.dbuf, s.dbuf + k * pitch, 0, pitch, 0, pitch, k};
+            const int vrc = core::verify_on_device(c, dev, L, 1, len, d_word, s.stream);
+            if (vrc) return vrc;
+            SHMR_HIP_TRY(hipMemcpyAsync(&word, d_word, sizeof(word), hipMemcpyDeviceToHost, s.stream));
+            return SHMR_EC_OK;
+        });
+        if (rc) return rc;
         *consistent = word == 0;
         return SHMR_EC_OK;
     });
@@ -744,7 +758,17 @@ struct shmr_ec_op {
     core::SubmitReq* req = nullptr; // or a request of the submission queue
 };
 
-static int start_op(int rc, core::Staging* s, core::SubmitReq* req, shmr_ec_op_t** op) {
+}  // extern "C"
+
+// A _start call: `call(&s, &req)` is the blocking call's body, which may leave
+// kernels running on a pooled stream or a request pending; *op takes them over.
+template <class Call>
+static int start_op(shmr_ec_op_t** op, Call&& call) {
+    if (!op) return SHMR_EC_INVALID_ARGUMENT;
+    *op = nullptr;
+    core::Staging* s = nullptr;
+    core::SubmitReq* req = nullptr;
+    const int rc = call(&s, &req);
     auto drop = [&] {
         if (s) (void)core::finish_async(s);
         if (req) {
@@ -769,43 +793,35 @@ static int start_op(int rc, core::Staging* s, core::SubmitReq* req, shmr_ec_op_t
     });
 }
 
+extern "C" {
+
 int shmr_ec_encode_start(shmr_ec_t* rs, uint8_t* const* shards, const size_t* shard_lens, size_t nshards,
                          shmr_ec_op_t** op) {
-    if (!op) return SHMR_EC_INVALID_ARGUMENT;
-    *op = nullptr;
-    core::Staging* s = nullptr;
-    core::SubmitReq* q = nullptr;
-    const int rc = encode_impl(rs, shards, shard_lens, nshards, &s, &q);
-    return start_op(rc, s, q, op);
+    return start_op(op, [&](core::Staging** s, core::SubmitReq** q) {
+        return encode_impl(rs, shards, shard_lens, nshards, s, q);
+    });
 }
 
 int shmr_ec_reconstruct_start(shmr_ec_t* rs, uint8_t* const* shards, const size_t* shard_lens, const uint8_t* present,
                               size_t nshards, int data_only, shmr_ec_op_t** op) {
-    if (!op) return SHMR_EC_INVALID_ARGUMENT;
-    *op = nullptr;
-    core::Staging* s = nullptr;
-    core::SubmitReq* q = nullptr;
-    const int rc = reconstruct_impl(rs, shards, shard_lens, present, nshards, data_only, &s, &q);
-    return start_op(rc, s, q, op);
+    return start_op(op, [&](core::Staging** s, core::SubmitReq** q) {
+        return reconstruct_impl(rs, shards, shard_lens, present, nshards, data_only, s, q);
+    });
 }
 
 int shmr_ec_encode_dev_start(shmr_ec_t* rs, uint8_t* const* d_shards, const size_t* shard_lens, size_t nshards,
                              int device, shmr_ec_op_t** op) {
-    if (!op) return SHMR_EC_INVALID_ARGUMENT;
-    *op = nullptr;
-    core::SubmitReq* q = nullptr;
-    const int rc = encode_dev_impl(rs, d_shards, shard_lens, nshards, device, &q);
-    return start_op(rc, nullptr, q, op);
+    return start_op(op, [&](core::Staging**, core::SubmitReq** q) {
+        return encode_dev_impl(rs, d_shards, shard_lens, nshards, device, q);
+    });
 }
 
 int shmr_ec_reconstruct_dev_start(shmr_ec_t* rs, uint8_t* const* d_shards, const size_t* shard_lens,
                                   const uint8_t* present, size_t nshards, int data_only, int device,
                                   shmr_ec_op_t** op) {
-    if (!op) return SHMR_EC_INVALID_ARGUMENT;
-    *op = nullptr;
-    core::SubmitReq* q = nullptr;
-    const int rc = reconstruct_dev_impl(rs, d_shards, shard_lens, present, nshards, data_only, device, &q);
-    return start_op(rc, nullptr, q, op);
+    return start_op(op, [&](core::Staging**, core::SubmitReq** q) {
+        return reconstruct_dev_impl(rs, d_shards, shard_lens, present, nshards, data_only, device, q);
+    });
 }
 
 int shmr_ec_op_wait(shmr_ec_op_t* op) {
@@ -826,17 +842,12 @@ int shmr_ec_encode_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_s
                              size_t shard_len, int device, void* stream) {
     return guarded([&]() -> int {
         if (!rs) return SHMR_EC_INVALID_ARGUMENT;
-        if (nblocks == 0) return SHMR_EC_OK;
-        if (shard_len == 0) return SHMR_EC_EMPTY_SHARD;
-        if (!d_data || !d_parity) return SHMR_EC_INVALID_ARGUMENT;
-        int rc = core::check_device(device);
-        if (rc) return rc;
-        core::DeviceScope scope(device);
-        if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
-        Codec& c = *rs->codec;
-        const core::Layout L{d_data, d_parity, data_block_pitch, data_shard_pitch, parity_block_pitch, parity_shard_pitch,
-                             c.k()};
-        return core::encode_on_device(c, device, L, nblocks, shard_len, static_cast<hipStream_t>(stream));
+        return batch_dev(nblocks, shard_len, device, [&] { return arg_ok(d_data && d_parity); }, [&] {
+            Codec& c = *rs->codec;
+            const core::Layout L{d_data, d_parity, data_block_pitch, data_shard_pitch, parity_block_pitch,
+                                 parity_shard_pitch, c.k()};
+            return core::encode_on_device(c, device, L, nblocks, shard_len, static_cast<hipStream_t>(stream));
+        });
     });
 }
 
@@ -845,19 +856,14 @@ int shmr_ec_verify_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_s
                              size_t nblocks, size_t shard_len, uint32_t* d_mismatch, int device, void* stream) {
     return guarded([&]() -> int {
         if (!rs) return SHMR_EC_INVALID_ARGUMENT;
-        if (nblocks == 0) return SHMR_EC_OK;
-        if (shard_len == 0) return SHMR_EC_EMPTY_SHARD;
-        if (!d_data || !d_parity || !d_mismatch) return SHMR_EC_INVALID_ARGUMENT;
-        if (uintptr_t(d_mismatch) % alignof(uint32_t)) return SHMR_EC_INVALID_ARGUMENT;
-        int rc = core::check_device(device);
-        if (rc) return rc;
-        core::DeviceScope scope(device);
-        if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
-        Codec& c = *rs->codec;
-        // (the layout's output side is the stored parity: the verify kernels only read it)
-        const core::Layout L{d_data, const_cast<uint8_t*>(d_parity), data_block_pitch, data_shard_pitch,
-                             parity_block_pitch, parity_shard_pitch, c.k()};
-        return core::verify_on_device(c, device, L, nblocks, shard_len, d_mismatch, static_cast<hipStream_t>(stream));
+        const bool given = d_data && d_parity && d_mismatch && uintptr_t(d_mismatch) % alignof(uint32_t) == 0;
+        return batch_dev(nblocks, shard_len, device, [&] { return arg_ok(given); }, [&] {
+            Codec& c = *rs->codec;
+            // (the layout's output side is the stored parity: the verify kernels only read it)
+            const core::Layout L{d_data, const_cast<uint8_t*>(d_parity), data_block_pitch, data_shard_pitch,
+                                 parity_block_pitch, parity_shard_pitch, c.k()};
+            return core::verify_on_device(c, device, L, nblocks, shard_len, d_mismatch, static_cast<hipStream_t>(stream));
+        });
     });
 }
 
@@ -866,18 +872,13 @@ int shmr_ec_reconstruct_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard
                                   void* stream) {
     return guarded([&]() -> int {
         if (!rs || !present) return SHMR_EC_INVALID_ARGUMENT;
-        if (nblocks == 0) return SHMR_EC_OK;
-        if (shard_len == 0) return SHMR_EC_EMPTY_SHARD;
-        if (!d_shards) return SHMR_EC_INVALID_ARGUMENT;
         Codec& c = *rs->codec;
-        int rc = core::validate_presence(c, present, nblocks);   // no launch on a bad batch
-        if (rc) return rc;
-        rc = core::check_device(device);
-        if (rc) return rc;
-        core::DeviceScope scope(device);
-        if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
-        return core::reconstruct_on_device(c, device, d_shards, shard_pitch, block_pitch, present, nblocks, shard_len,
-                                           data_only != 0, static_cast<hipStream_t>(stream));
+        // (no launch on a bad batch)
+        auto check = [&] { return d_shards ? core::validate_presence(c, present, nblocks) : arg_ok(false); };
+        return batch_dev(nblocks, shard_len, device, check, [&] {
+            return core::reconstruct_on_device(c, device, d_shards, shard_pitch, block_pitch, present, nblocks, shard_len,
+                                               data_only != 0, static_cast<hipStream_t>(stream));
+        });
     });
 }
 
@@ -887,20 +888,15 @@ int shmr_ec_reconstruct_batch_dev_out(shmr_ec_t* rs, const uint8_t* d_shards, si
                                       void* stream) {
     return guarded([&]() -> int {
         if (!rs || !present) return SHMR_EC_INVALID_ARGUMENT;
-        if (nblocks == 0) return SHMR_EC_OK;
-        if (shard_len == 0) return SHMR_EC_EMPTY_SHARD;
-        if (!d_shards || !d_out) return SHMR_EC_INVALID_ARGUMENT;
         Codec& c = *rs->codec;
-        int rc = core::validate_presence(c, present, nblocks);   // no launch on a bad batch
-        if (rc) return rc;
-        rc = core::check_device(device);
-        if (rc) return rc;
-        core::DeviceScope scope(device);
-        if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
-        core::Layout L{d_shards, d_out, block_pitch, shard_pitch, out_block_pitch, out_shard_pitch, 0};
-        L.compact = true;
-        return core::reconstruct_on_device(c, device, L, present, nblocks, shard_len, data_only != 0,
-                                           static_cast<hipStream_t>(stream));
+        // (no launch on a bad batch)
+        auto check = [&] { return d_shards && d_out ? core::validate_presence(c, present, nblocks) : arg_ok(false); };
+        return batch_dev(nblocks, shard_len, device, check, [&] {
+            core::Layout L{d_shards, d_out, block_pitch, shard_pitch, out_block_pitch, out_shard_pitch, 0};
+            L.compact = true;
+            return core::reconstruct_on_device(c, device, L, present, nblocks, shard_len, data_only != 0,
+                                               static_cast<hipStream_t>(stream));
+        });
     });
 }
 
@@ -915,25 +911,16 @@ static int ptrs_dev(shmr_ec_t* rs, uint8_t* const* d_shards, const uint8_t* pres
     return guarded([&]() -> int {
         if (!rs || !d_shards) return SHMR_EC_INVALID_ARGUMENT;
         if (op == core::kDecode && !present) return SHMR_EC_INVALID_ARGUMENT;
-        if (nblocks == 0) return SHMR_EC_OK;
-        if (shard_len == 0) return SHMR_EC_EMPTY_SHARD;
         Codec& c = *rs->codec;
-        const unsigned k = c.k(), t = k + c.p();
-        int rc = SHMR_EC_OK;
-        if (op == core::kDecode && (rc = core::validate_presence(c, present, nblocks))) return rc;
-        for (size_t b = 0; b < nblocks; ++b)
-            for (unsigned i = 0; i < t; ++i) {
-                // absent parity under data_only is neither read nor written
-                const bool needed = op == core::kEncode || present[b * t + i] || i < k || !data_only;
-                if (needed && !d_shards[b * t + i]) return SHMR_EC_INVALID_ARGUMENT;
-            }
-        rc = core::check_device(device);
-        if (rc) return rc;
-        core::DeviceScope scope(device);
-        if (!scope.ok()) return SHMR_EC_DEVICE_ERROR;
-        static_assert(sizeof(uint8_t*) == sizeof(uint64_t), "64-bit device pointers");
-        return core::ptrs_launch(c, reinterpret_cast<const uint64_t*>(d_shards), present, nblocks, shard_len,
-                                 data_only != 0, device, static_cast<hipStream_t>(stream_), op, false, true);
+        auto check = [&] {
+            const int rc = op == core::kDecode ? core::validate_presence(c, present, nblocks) : SHMR_EC_OK;
+            return rc ? rc : arg_ok(needed_shards_given(d_shards, present, nblocks, c.k(), c.k() + c.p(), data_only != 0));
+        };
+        return batch_dev(nblocks, shard_len, device, check, [&] {
+            static_assert(sizeof(uint8_t*) == sizeof(uint64_t), "64-bit device pointers");
+            return core::ptrs_launch(c, reinterpret_cast<const uint64_t*>(d_shards), present, nblocks, shard_len,
+                                     data_only != 0, device, static_cast<hipStream_t>(stream_), op, false, true);
+        });
     });
 }
 
@@ -956,18 +943,10 @@ static int host_batch(shmr_ec_t* rs, uint8_t* const* host_shards, const uint8_t*
         if (nblocks == 0) return SHMR_EC_OK;
         if (shard_len == 0) return SHMR_EC_EMPTY_SHARD;
         Codec& c = *rs->codec;
-        const unsigned t = c.k() + c.p();
-        for (size_t b = 0; b < nblocks; ++b)
-            for (unsigned i = 0; i < t; ++i) {
-                // absent shards of a decode still need an output buffer (unless
-                // they are parity under data_only)
-                const bool needed = op == core::kEncode || present[b * t + i] || i < c.k() || !data_only;
-                if (needed && !host_shards[b * t + i]) return SHMR_EC_INVALID_ARGUMENT;
-            }
-        for (int d = 0; d < ndev; ++d) {
-            int rc = core::check_device(devices[d]);
-            if (rc) return rc;
-        }
+        // (absent shards of a decode still need an output buffer)
+        int rc = arg_ok(needed_shards_given(host_shards, present, nblocks, c.k(), c.k() + c.p(), data_only != 0));
+        for (int d = 0; d < ndev && !rc; ++d) rc = core::check_device(devices[d]);
+        if (rc) return rc;
         core::HostJob job{c, op, data_only != 0, host_shards, present, nblocks, shard_len, 64ull << 20,
                           core::copy_threads_default()};
         return core::run_host_job(job, devices, ndev);

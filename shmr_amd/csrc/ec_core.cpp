@@ -8,6 +8,7 @@
 #include <unordered_map>
 #include <unordered_set>
 
+#include "knobs.hpp"
 #include "run_split.hpp"
 
 namespace shmr {
@@ -16,7 +17,9 @@ namespace core {
 // ===========================================================================
 // Tuning.  kAuto knobs follow kern::policy_variant: the fastest variants measured
 // on MI355X per launch shape (tools/tune.py, interleaved A/B in one process;
-// DESIGN.md "Tuning").  set_tuning() pins a knob explicitly.
+// DESIGN.md "Tuning").  set_tuning() pins a knob explicitly.  The knobs' values
+// live in the atomics below, which the code they steer loads directly; their
+// names, ranges and kern::Variant members are the rows of kKnobs (further down).
 // ===========================================================================
 namespace {
 
@@ -57,7 +60,7 @@ std::atomic<int> g_alias_devices{0};   // tools build: alias device IDs (see ec_
 // Reconstructs over device shard-pointer tables take segment launches (plans in
 // the kernel arguments) when they fit; 0 = always the uploaded block/plan table
 std::atomic<int> g_ptrs_segs{1};
-// Pointer tables that name a slot grid (ec_api.cpp ptrs_as_grid) take the strided kernels
+// Pointer tables that name a slot grid (ptrs.cpp lattice_form) take the strided kernels
 // of the *_batch_dev calls; 0 = always the table kernels
 std::atomic<int> g_ptrs_grid{1};
 // Misaligned device-resident shards: kAuto = the vector kernels (modes 0 / 1)
@@ -108,237 +111,109 @@ std::atomic<int> g_lattice_list{0};
 //    scalar loads of the block's table row) for RS(8,3) encode (+1.8) and
 //    every rebuild (+3.4 / +8.2 with sc1); RS(10,4) encode keeps the plain tile.
 
-bool split_key(const char* key, std::string* k, int* first, int* last) {
-    if (!key) return false;
-    *k = key;
-    *first = kEncode;
-    *last = kDecode;
-    if (k->rfind("encode.", 0) == 0) {
-        *first = *last = kEncode;
-        *k = k->substr(7);
-    } else if (k->rfind("decode.", 0) == 0) {
-        *first = *last = kDecode;
-        *k = k->substr(7);
-    }
-    return true;
+bool aligned16(uint64_t v) { return (v & 15u) == 0; }
+
+// ---- the knob table: every knob of this file, once (knobs.hpp) ---------------
+static_assert(kAuto == knobs::kAuto && SHMR_EC_OK == knobs::kOk && SHMR_EC_INVALID_ARGUMENT == knobs::kInvalid,
+              "knobs.hpp restates these");
+using V = kern::Variant;
+using K = knobs::Knob<V>;
+using knobs::among;
+using knobs::any;
+using knobs::range;
+
+// Kernel knobs: per op class.  They exist to take measurements and live in the
+// tools build (libshmr_ec_tools.so).  In the product build the kernel variant
+// of every launch is the measured policy (kern::policy_variant), the same for
+// every caller in the process, and a knob may only be "set" to its default; in
+// particular "diag" (XOR-only, wrong results) is refused.
+K kernel_knob(const char* name, std::atomic<int> Tuning::*m, int dflt, bool auto_ok, knobs::Accept a, bool to_bool,
+              knobs::Use use, int V::*vi, bool V::*vb, bool tail) {
+    return knobs::tools_only(K{name, knobs::kPerClass, {&(g_tune[kEncode].*m), &(g_tune[kDecode].*m)}, dflt, auto_ok,
+                               a, a, to_bool, use, vi, vb, tail});
+}
+// kAuto = the policy's choice, else on / off
+K flag(const char* name, std::atomic<int> Tuning::*m, bool V::*vb, bool tail = false,
+       knobs::Use use = knobs::kOverride) {
+    return kernel_knob(name, m, kAuto, true, any(), true, use, nullptr, vb, tail);
+}
+// kAuto = the policy's choice, else one of the listed values
+K number(const char* name, std::atomic<int> Tuning::*m, knobs::Accept a, int V::*vi) {
+    return kernel_knob(name, m, kAuto, true, a, false, knobs::kOverride, vi, nullptr, false);
+}
+// Process-wide knobs: one value, whatever class prefix the key carries.
+K process_knob(const char* name, std::atomic<int>* at, int dflt, knobs::Accept a, bool to_bool = false) {
+    return K{name, knobs::kProcess, {at, at}, dflt, true, a, a, to_bool, knobs::kStored, nullptr, nullptr, false};
 }
 
-bool aligned16(uint64_t v) { return (v & 15u) == 0; }
+const K kKnobs[] = {
+    number("chunks", &Tuning::u, among(1, 2, 4), &V::u),   // tools build: verify_chunks reads encode.chunks
+    flag("nt_load", &Tuning::nt_load, &V::nt_load),
+    flag("nt_store", &Tuning::nt_store, &V::nt_store),
+    // no kAuto: stores value != 0, so -2 stores 1 in the tools build
+    kernel_knob("occ8", &Tuning::occ8, 0, false, any(), true, knobs::kOverride, nullptr, &V::occ8, false),
+    // no kAuto: any value >= -1; read by grid_mode()
+    kernel_knob("grid", &Tuning::grid, -1, false, range(-1, INT_MAX), false, knobs::kStored, nullptr, nullptr, false),
+    // no kAuto: stores value != 0, so -2 stores 1 in the tools build
+    kernel_knob("diag", &Tuning::diag, 0, false, any(), true, knobs::kOverride, nullptr, &V::diag, false),
+    kernel_knob("threads", &Tuning::threads, 256, false, among(128, 256, 512), false, knobs::kOverride, &V::threads,
+                nullptr, false),
+    number("depth", &Tuning::depth, among(1, 2, 3, 5, 9), &V::depth),
+    number("wgs_per_cu", &Tuning::wgs_per_cu, range(0, 32), &V::wgs_per_cu),
+    number("occ", &Tuning::occ, among(0, 5, 6, 7), &V::occ),
+    flag("early", &Tuning::early, &V::early),
+    flag("spre", &Tuning::spre, &V::spre),
+    flag("fuse_tail", &Tuning::fuse_tail, &V::fuse_tail, false, knobs::kOnlyOff),   // only 0 overrides the policy
+    flag("glds", &Tuning::glds, &V::glds, true),
+    flag("serial", &Tuning::serial, &V::serial, true),
+    flag("sc1_store", &Tuning::sc1_store, &V::sc1_store, true),
+    flag("realign", &Tuning::realign, &V::realign, true, knobs::kStored),   // stored; applied in launch_set
+    flag("peel", &Tuning::peel, &V::peel, true),
+    flag("wave_run", &Tuning::wave_run, &V::wave_run, true),   // its kAuto is a rule of select_variant
+    flag("st_align", &Tuning::st_align, &V::st_align, true, knobs::kStored),   // stored; applied in launch_set
+    flag("xcd", &Tuning::xcd, &V::xcd, true),
+    flag("pair", &Tuning::pair, &V::pair, true),
+    // any value >= 0; kAuto resets these three to their measured defaults
+    process_knob("bounce_kib", &g_bounce_kib, kBounceKibDefault, range(0, INT_MAX)),
+    process_knob("ptrs_direct", &g_ptrs_direct, kPtrsDirectDefault, range(0, INT_MAX)),
+    process_knob("sync_spin_us", &g_sync_spin, kSyncSpinDefault, range(0, INT_MAX)),
+    process_knob("mirror_zc", &g_mirror_zc, 1, any(), true),
+    process_knob("ptrs_segs", &g_ptrs_segs, 1, any(), true),
+    process_knob("ptrs_grid", &g_ptrs_grid, 1, any(), true),
+    // kAuto is stored as such (see g_uvec); 1 in the tools build only
+    K{"uvec", knobs::kProcess, {&g_uvec, &g_uvec}, kAuto, true, among(0, 1), among(0), false, knobs::kStored, nullptr,
+      nullptr, false},
+    process_knob("pattern_launches", &g_pattern_launches, 0, any(), true),
+    process_knob("lattice_list", &g_lattice_list, 0, among(0, 1)),
+    // tools build only: the product build answers OK for 0 or -2 and INVALID_ARGUMENT for anything else
+    knobs::tools_only(process_knob("slots_list", &g_slots_list, 0, among(0, 1))),
+    knobs::tools_only(process_knob("alias_devices", &g_alias_devices, 0, range(0, 32))),   // (see ec_core.hpp)
+};
 
 }  // namespace
 
 int set_tuning(const char* key, int value) {
-    std::string k;
-    int first = 0, last = 1;
-    if (!split_key(key, &k, &first, &last)) return SHMR_EC_INVALID_ARGUMENT;
-    if (k == "bounce_kib") {   // not per op class
-        if (value < 0 && value != kAuto) return SHMR_EC_INVALID_ARGUMENT;
-        g_bounce_kib = value == kAuto ? kBounceKibDefault : value;
-        return SHMR_EC_OK;
-    }
-    if (k == "mirror_zc") {
-        g_mirror_zc = value == kAuto ? 1 : (value != 0);
-        return SHMR_EC_OK;
-    }
-    if (k == "ptrs_segs") {
-        g_ptrs_segs = value == kAuto ? 1 : (value != 0);
-        return SHMR_EC_OK;
-    }
-    if (k == "ptrs_grid") {
-        g_ptrs_grid = value == kAuto ? 1 : (value != 0);
-        return SHMR_EC_OK;
-    }
-    if (k == "ptrs_direct") {
-        if (value < 0 && value != kAuto) return SHMR_EC_INVALID_ARGUMENT;
-        g_ptrs_direct = value == kAuto ? kPtrsDirectDefault : value;
-        return SHMR_EC_OK;
-    }
-    if (k == "sync_spin_us") {
-        if (value < 0 && value != kAuto) return SHMR_EC_INVALID_ARGUMENT;
-        g_sync_spin = value == kAuto ? kSyncSpinDefault : value;
-        return SHMR_EC_OK;
-    }
-    if (k == "uvec") {   // not per op class; the product build takes kAuto and 0
-#ifdef SHMR_EC_TOOLS
-        if (value != kAuto && value != 0 && value != 1) return SHMR_EC_INVALID_ARGUMENT;
-#else
-        if (value != kAuto && value != 0) return SHMR_EC_INVALID_ARGUMENT;
-#endif
-        g_uvec = value;
-        return SHMR_EC_OK;
-    }
-    if (k == "pattern_launches") {   // not per op class
-        g_pattern_launches = value == kAuto ? 0 : (value != 0);
-        return SHMR_EC_OK;
-    }
-    if (k == "lattice_list") {   // not per op class
-        if (value != kAuto && value != 0 && value != 1) return SHMR_EC_INVALID_ARGUMENT;
-        g_lattice_list = value == kAuto ? 0 : value;
-        return SHMR_EC_OK;
-    }
-    if (k == "slots_list") {   // not per op class; tools build only
-        const int v = value == kAuto ? 0 : value;
-#ifdef SHMR_EC_TOOLS
-        if (v != 0 && v != 1) return SHMR_EC_INVALID_ARGUMENT;
-        g_slots_list = v;
-        return SHMR_EC_OK;
-#else
-        return v == 0 ? SHMR_EC_OK : SHMR_EC_INVALID_ARGUMENT;
-#endif
-    }
-    if (k == "alias_devices") {   // not per op class; tools build only (see ec_core.hpp)
-        const int v = value == kAuto ? 0 : value;
-#ifdef SHMR_EC_TOOLS
-        if (v < 0 || v > 32) return SHMR_EC_INVALID_ARGUMENT;
-        g_alias_devices = v;
-        return SHMR_EC_OK;
-#else
-        return v == 0 ? SHMR_EC_OK : SHMR_EC_INVALID_ARGUMENT;
-#endif
-    }
-#ifndef SHMR_EC_TOOLS
-    // Product build: the kernel variant of every launch is the measured policy
-    // (kern::policy_variant), the same for every caller in the process.  Kernel knobs
-    // exist to take measurements and live in the tools build
-    // (libshmr_ec_tools.so); here a knob may only be "set" to its default.
-    // In particular "diag" (XOR-only, wrong results) is refused.
-    {
-        static const std::map<std::string, int> kDefaults = {
-            {"chunks", kAuto}, {"nt_load", kAuto}, {"nt_store", kAuto}, {"occ8", 0},
-            {"grid", -1},      {"diag", 0},        {"threads", 256},    {"depth", kAuto},   {"wgs_per_cu", kAuto},
-            {"occ", kAuto},    {"early", kAuto},   {"spre", kAuto},     {"fuse_tail", kAuto},
-            {"glds", kAuto},   {"serial", kAuto},   {"sc1_store", kAuto}, {"realign", kAuto}, {"peel", kAuto}, {"wave_run", kAuto}, {"st_align", kAuto},
-            {"xcd", kAuto},    {"pair", kAuto}};
-        const auto it = kDefaults.find(k);
-        return (it != kDefaults.end() && it->second == value) ? SHMR_EC_OK : SHMR_EC_INVALID_ARGUMENT;
-    }
-#endif
-    for (int i = first; i <= last; ++i) {
-        Tuning& T = g_tune[i];
-        if (k == "chunks") {
-            if (value != 1 && value != 2 && value != 4 && value != kAuto) return SHMR_EC_INVALID_ARGUMENT;
-            T.u = value;
-        } else if (k == "nt_load") {
-            T.nt_load = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "nt_store") {
-            T.nt_store = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "occ8") {
-            T.occ8 = value != 0;
-        } else if (k == "grid") {
-            if (value < -1) return SHMR_EC_INVALID_ARGUMENT;
-            T.grid = value;
-        } else if (k == "diag") {
-            T.diag = value != 0;
-        } else if (k == "threads") {
-            if (value != 128 && value != 256 && value != 512) return SHMR_EC_INVALID_ARGUMENT;
-            T.threads = value;
-        } else if (k == "depth") {
-            if (value != 1 && value != 2 && value != 3 && value != 5 && value != 9 && value != kAuto) return SHMR_EC_INVALID_ARGUMENT;
-            T.depth = value;
-        } else if (k == "wgs_per_cu") {
-            if ((value < 0 || value > 32) && value != kAuto) return SHMR_EC_INVALID_ARGUMENT;
-            T.wgs_per_cu = value;
-        } else if (k == "occ") {
-            if (value != 0 && value != 5 && value != 6 && value != 7 && value != kAuto) return SHMR_EC_INVALID_ARGUMENT;
-            T.occ = value;
-        } else if (k == "early") {
-            T.early = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "spre") {
-            T.spre = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "fuse_tail") {
-            T.fuse_tail = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "glds") {
-            T.glds = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "serial") {
-            T.serial = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "sc1_store") {
-            T.sc1_store = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "realign") {
-            T.realign = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "peel") {
-            T.peel = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "wave_run") {
-            T.wave_run = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "st_align") {
-            T.st_align = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "xcd") {
-            T.xcd = value == kAuto ? kAuto : (value != 0);
-        } else if (k == "pair") {
-            T.pair = value == kAuto ? kAuto : (value != 0);
-        } else {
-            return SHMR_EC_INVALID_ARGUMENT;
-        }
-    }
-    return SHMR_EC_OK;
+    bool known = false;
+    return knobs::knob_set(kKnobs, key, value, &known);
 }
 
+// (of an unprefixed per-class key: the encode value)
 int get_tuning(const char* key) {
-    std::string k;
-    int first = 0, last = 1;
-    if (!split_key(key, &k, &first, &last)) return SHMR_EC_INVALID_ARGUMENT;
-    const Tuning& T = g_tune[first];
-    if (k == "bounce_kib") return g_bounce_kib;
-    if (k == "mirror_zc") return g_mirror_zc;
-    if (k == "ptrs_segs") return g_ptrs_segs;
-    if (k == "ptrs_grid") return g_ptrs_grid;
-    if (k == "ptrs_direct") return g_ptrs_direct;
-    if (k == "sync_spin_us") return g_sync_spin;
-    if (k == "alias_devices") return g_alias_devices;
-    if (k == "slots_list") return g_slots_list;
-    if (k == "lattice_list") return g_lattice_list;
-    if (k == "pattern_launches") return g_pattern_launches;
-    if (k == "uvec") return g_uvec;
-    if (k == "chunks") return T.u;
-    if (k == "nt_load") return T.nt_load;
-    if (k == "nt_store") return T.nt_store;
-    if (k == "occ8") return T.occ8;
-    if (k == "grid") return T.grid;
-    if (k == "diag") return T.diag;
-    if (k == "threads") return T.threads;
-    if (k == "depth") return T.depth;
-    if (k == "wgs_per_cu") return T.wgs_per_cu;
-    if (k == "occ") return T.occ;
-    if (k == "early") return T.early;
-    if (k == "spre") return T.spre;
-    if (k == "fuse_tail") return T.fuse_tail;
-    if (k == "glds") return T.glds;
-    if (k == "serial") return T.serial;
-    if (k == "sc1_store") return T.sc1_store;
-    if (k == "realign") return T.realign;
-    if (k == "peel") return T.peel;
-    if (k == "wave_run") return T.wave_run;
-    if (k == "st_align") return T.st_align;
-    if (k == "xcd") return T.xcd;
-    if (k == "pair") return T.pair;
-    return SHMR_EC_INVALID_ARGUMENT;
+    bool known = false;
+    return knobs::knob_get(kKnobs, key, &known);
+}
+
+void describe_variant_tail(const kern::Variant& v, char* buf, size_t len) {
+    knobs::knob_describe_tail(kKnobs, v, buf, len);
 }
 
 kern::Variant select_variant(OpClass op, const kern::LaunchShape& s) {
     kern::Variant v = kern::policy_variant(s);
 #ifdef SHMR_EC_TOOLS
-    // Tools build: explicit knobs override the policy (measurement variants).
-    const Tuning& T = g_tune[op];
-    if (T.u.load() != kAuto) v.u = T.u.load();
-    if (T.nt_load.load() != kAuto) v.nt_load = T.nt_load.load() != 0;
-    if (T.nt_store.load() != kAuto) v.nt_store = T.nt_store.load() != 0;
-    v.occ8 = T.occ8.load() != 0;
-    v.diag = T.diag.load() != 0;
-    v.threads = T.threads.load();
-    if (T.depth.load() != kAuto) v.depth = T.depth.load();
-    if (T.wgs_per_cu.load() != kAuto) v.wgs_per_cu = T.wgs_per_cu.load();
-    if (T.occ.load() != kAuto) v.occ = T.occ.load();
-    if (T.early.load() != kAuto) v.early = T.early.load() != 0;
-    if (T.spre.load() != kAuto) v.spre = T.spre.load() != 0;
-    if (T.fuse_tail.load() == 0) v.fuse_tail = false;
-    if (T.glds.load() != kAuto) v.glds = T.glds.load() != 0;
-    if (T.serial.load() != kAuto) v.serial = T.serial.load() != 0;
-    if (T.sc1_store.load() != kAuto) v.sc1_store = T.sc1_store.load() != 0;
-    if (T.peel.load() != kAuto) v.peel = T.peel.load() != 0;
-    if (T.xcd.load() != kAuto) v.xcd = T.xcd.load() != 0;
-    if (T.pair.load() != kAuto) v.pair = T.pair.load() != 0;
-    if (T.wave_run.load() != kAuto)
-        v.wave_run = T.wave_run.load() != 0;
-    else
+    // Tools build: explicit knobs override the policy (measurement variants);
+    // then the rules between knobs.
+    knobs::knob_override(kKnobs, op, &v);
+    if (g_tune[op].wave_run.load() == kAuto)
         v.wave_run = v.u > 1 && v.nt_load && v.depth == 2 && v.threads == 256 && !v.occ8 && !s.host_mapped &&
                      !v.glds && !v.spre;
     if (v.sc1_store) v.nt_store = false;        // one store policy per kernel

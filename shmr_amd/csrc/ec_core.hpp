@@ -39,6 +39,8 @@ int get_tuning(const char* key);
 // The full-tile variant of a launch shape: kern::policy_variant (gf_apply.hpp),
 // plus the tools build's kernel knobs.
 kern::Variant select_variant(OpClass op, const kern::LaunchShape& s);
+// Appends " name=1" to buf for each set flag a variant description lists only then.
+void describe_variant_tail(const kern::Variant& v, char* buf, size_t len);
 kern::LaunchShape shape_of(OpClass op, unsigned k, unsigned rows, bool host_mapped, bool ptrs, bool segs,
                            bool compact, bool sc1_ok, bool fused);
 // Whether segment launches are compiled for this op's current tuning (always,

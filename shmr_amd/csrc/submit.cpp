@@ -39,6 +39,7 @@
 #include <tuple>
 
 #include "gf_apply.hpp"
+#include "knobs.hpp"
 
 namespace shmr {
 namespace core {
@@ -675,43 +676,32 @@ int wait(SubmitReq* r) {
 
 bool coalesce_host() { return g_coalesce.load(std::memory_order_relaxed) != 0; }
 
-int set_submit_tuning(const std::string& key, int value, bool* known) {
-    *known = true;
-    auto set = [&](std::atomic<int>& v, int dflt, int lo, int hi) {
-        if (value == kAuto) value = dflt;
-        if (value < lo || value > hi) return SHMR_EC_INVALID_ARGUMENT;
-        v = value;
-        return SHMR_EC_OK;
-    };
-    if (key == "coalesce") return set(g_coalesce, 0, 0, 1);
-    if (key == "coalesce_depth") return set(g_depth, kDepthDefault, 1, 64);
-    if (key == "coalesce_target") return set(g_target, kTargetDefault, 1, 65536);
-    if (key == "coalesce_us") return set(g_window_us, kWindowDefault, 0, 100000);
-    if (key == "coalesce_max") return set(g_max, kMaxDefault, 1, 65536);
-    if (key == "coalesce_spin_us") return set(g_spin_us, kSpinDefault, 0, 10000000);
-    if (key == "coalesce_watch_us") return set(g_watch_us, kWatchDefault, 0, 10000000);
-    if (key == "coalesce_mark") return set(g_mark, 1, 0, 1);
-    if (key == "coalesce_lead_us") return set(g_lead_us, kLeadDefault, 0, 10000000);
-    if (key == "coalesce_idle_us") return set(g_idle_us, kIdleDefault, 0, 10000000);
-    *known = false;
-    return SHMR_EC_INVALID_ARGUMENT;
+namespace {
+struct NoVariant {};
+using K = knobs::Knob<NoVariant>;
+// The queue's knobs (knobs.hpp): process-wide, named by the bare key only
+// ("encode.coalesce" is no knob), kAuto = the default, else lo .. hi.
+K queue_knob(const char* name, std::atomic<int>* at, int dflt, int lo, int hi) {
+    return K{name, knobs::kExact, {at, at}, dflt, true, knobs::range(lo, hi), knobs::range(lo, hi), false,
+             knobs::kStored, nullptr, nullptr, false};
 }
+const K kKnobs[] = {
+    queue_knob("coalesce", &g_coalesce, 0, 0, 1),
+    queue_knob("coalesce_depth", &g_depth, kDepthDefault, 1, 64),
+    queue_knob("coalesce_target", &g_target, kTargetDefault, 1, 65536),
+    queue_knob("coalesce_us", &g_window_us, kWindowDefault, 0, 100000),
+    queue_knob("coalesce_max", &g_max, kMaxDefault, 1, 65536),
+    queue_knob("coalesce_spin_us", &g_spin_us, kSpinDefault, 0, 10000000),
+    queue_knob("coalesce_watch_us", &g_watch_us, kWatchDefault, 0, 10000000),
+    queue_knob("coalesce_mark", &g_mark, 1, 0, 1),
+    queue_knob("coalesce_lead_us", &g_lead_us, kLeadDefault, 0, 10000000),
+    queue_knob("coalesce_idle_us", &g_idle_us, kIdleDefault, 0, 10000000),
+};
+}  // namespace
 
-int get_submit_tuning(const std::string& key, bool* known) {
-    *known = true;
-    if (key == "coalesce") return g_coalesce;
-    if (key == "coalesce_depth") return g_depth;
-    if (key == "coalesce_target") return g_target;
-    if (key == "coalesce_us") return g_window_us;
-    if (key == "coalesce_max") return g_max;
-    if (key == "coalesce_spin_us") return g_spin_us;
-    if (key == "coalesce_watch_us") return g_watch_us;
-    if (key == "coalesce_mark") return g_mark;
-    if (key == "coalesce_lead_us") return g_lead_us;
-    if (key == "coalesce_idle_us") return g_idle_us;
-    *known = false;
-    return SHMR_EC_INVALID_ARGUMENT;
-}
+int set_submit_tuning(const char* key, int value, bool* known) { return knobs::knob_set(kKnobs, key, value, known); }
+
+int get_submit_tuning(const char* key, bool* known) { return knobs::knob_get(kKnobs, key, known); }
 
 void submit_stats(int dev, uint64_t* out, size_t n) {
     for (size_t i = 0; i < n && i < size_t(kStatCount); ++i)

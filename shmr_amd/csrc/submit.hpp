@@ -77,8 +77,8 @@ int wait(SubmitReq* r);
 // is queued behind it and the GPU does not idle between batches; 0: only at
 // its completion).
 bool coalesce_host();
-int set_submit_tuning(const std::string& key, int value, bool* known);
-int get_submit_tuning(const std::string& key, bool* known);
+int set_submit_tuning(const char* key, int value, bool* known);
+int get_submit_tuning(const char* key, bool* known);
 
 // Queue statistics of a device ID: requests, launches (batches), the largest
 // batch, waits that slept (blocking event sync) -- shmr_ec_queue_stats.

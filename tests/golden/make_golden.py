@@ -15,6 +15,13 @@ Two kinds of data, kept apart on purpose:
   quirks).  These are the build's own pins (regression vectors).
 
 Run:  python tests/golden/make_golden.py
+
+* tuning_table.json -- what the two native libraries answer to the tuning
+  calls (every knob, key form and value) and their describe strings: recorded
+  from a build of the commit whose behaviour is to be kept, replayed by
+  tests/test_abi.py.
+
+Run:  python tests/golden/make_golden.py tuning_table <directory of the two libraries>
 """
 from __future__ import annotations
 
@@ -163,7 +170,120 @@ def glue_cases():
     return cases
 
 
+TUNING_VALUES = [-3, -2, -1, 0, 1, 2, 3, 4, 5, 6, 7, 9, 32, 33, 64, 128, 256, 512, 65536, 65537, 10000001]
+KERNEL_FLAGS = ["nt_load", "nt_store", "occ8", "diag", "early", "spre", "fuse_tail", "glds", "serial", "sc1_store",
+                "realign", "peel", "wave_run", "st_align", "xcd", "pair"]
+# kernel knob -> the non-default values its describe strings are recorded under
+KERNEL_KNOBS = {"chunks": [2], "grid": [0], "threads": [128], "depth": [3], "wgs_per_cu": [4], "occ": [6],
+                **{name: [0, 1] for name in KERNEL_FLAGS}}
+PROCESS_KNOBS = ["bounce_kib", "mirror_zc", "ptrs_segs", "ptrs_grid", "ptrs_direct", "sync_spin_us", "uvec",
+                 "pattern_launches", "lattice_list", "slots_list", "alias_devices"]
+SUBMIT_KNOBS = ["coalesce", "coalesce_depth", "coalesce_target", "coalesce_us", "coalesce_max", "coalesce_spin_us",
+                "coalesce_watch_us", "coalesce_mark", "coalesce_lead_us", "coalesce_idle_us"]
+TUNING_NAMES = list(KERNEL_KNOBS) + PROCESS_KNOBS + SUBMIT_KNOBS + ["no_such_knob", "encode.coalesce",
+                                                                    "encode.bounce_kib"]
+TUNING_RESET = {"occ8": 0, "diag": 0, "threads": 256, "grid": -1}   # every other knob resets with -2
+
+
+def tuning_record(L):
+    """What one library (a ctypes handle with shmr_amd._native's signatures)
+    answers to the tuning calls; no device is touched.  "keys": per name one
+    row for each form of the key (bare, with "encode.", with "decode."): per
+    TUNING_VALUES entry the status of shmr_ec_set_tuning, then shmr_ec_get_tuning
+    of the three forms, the knob reset after each entry.  "describe": shmr_ec_describe_variant
+    for decode 0..4 x data_shards {4, 8, 9, 10} x rows 1..5 at default tuning
+    and, in the tools build, under each kernel knob set alone."""
+    import ctypes
+
+    def reset(name):
+        L.shmr_ec_set_tuning(name.encode(), TUNING_RESET.get(name, -2))
+
+    def describe():
+        buf, out = ctypes.create_string_buffer(512), []
+        for decode in range(5):
+            for k in (4, 8, 9, 10):
+                for rows in range(1, 6):
+                    rc = L.shmr_ec_describe_variant(decode, k, rows, buf, len(buf))
+                    out.append(buf.value.decode() if rc == 0 else f"status {rc}")
+        return out
+
+    keys = {}
+    for name in TUNING_NAMES:
+        forms = [f.encode() for f in (name, "encode." + name, "decode." + name)]
+        keys[name] = []
+        for key in forms:
+            row = []
+            for v in TUNING_VALUES:
+                row.append(L.shmr_ec_set_tuning(key, v))
+                row += [L.shmr_ec_get_tuning(f) for f in forms]
+                reset(name)
+            keys[name].append(row)
+    desc = {"default": describe()}
+    if L.shmr_ec_is_tools_build():
+        for name, values in KERNEL_KNOBS.items():
+            for cls in ("encode.", "decode."):
+                for v in values:
+                    assert L.shmr_ec_set_tuning((cls + name).encode(), v) == 0, (cls, name, v)
+                    desc[f"{cls}{name}={v}"] = describe()
+                    reset(name)
+        assert describe() == desc["default"]
+    return {"keys": keys, "describe": desc}
+
+
+def _interned(table, item):
+    """Index of `item` in `table` (appended when new): rows and strings repeat."""
+    if item not in table:
+        table.append(item)
+    return table.index(item)
+
+
+def tuning_table(lib_dir):
+    """tests/golden/tuning_table.json from the two libraries in `lib_dir`
+    (built from the commit whose behaviour is to be kept)."""
+    import ctypes
+    from shmr_amd import _native
+    out = {"values": TUNING_VALUES, "rows": [], "strings": []}
+    for flavour, so in (("product", "libshmr_ec.so"), ("tools", "libshmr_ec_tools.so")):
+        L = ctypes.CDLL(os.path.join(lib_dir, so))
+        for name, res, args in _native.SIGNATURES:
+            getattr(L, name).restype, getattr(L, name).argtypes = res, args
+        rec = tuning_record(L)
+        assert tuning_record(L) == rec, "not reproducible within one process"
+        out[flavour + ".keys"] = {k: [_interned(out["rows"], r) for r in rows]
+                                   for k, rows in rec["keys"].items()}
+        out[flavour + ".describe"] = {c: [_interned(out["strings"], s) for s in d]
+                                      for c, d in rec["describe"].items()}
+    return out
+
+
+def tuning_unpacked(table, flavour):
+    """The tuning_record() a packed tuning_table() holds for one flavour."""
+    return {"keys": {k: [table["rows"][i] for i in rows] for k, rows in table[flavour + ".keys"].items()},
+            "describe": {c: [table["strings"][i] for i in d] for c, d in table[flavour + ".describe"].items()}}
+
+
+def write_tuning_table(lib_dir):
+    """One table entry per line (compact, and a change shows as changed lines)."""
+    def dumps(x):
+        return json.dumps(x, separators=(",", ":"))
+    table, parts = tuning_table(lib_dir), []
+    for name, value in table.items():
+        if isinstance(value, dict):
+            body = ",\n".join(f"{dumps(k)}:{dumps(v)}" for k, v in value.items())
+            parts.append(f"{dumps(name)}:{{\n{body}\n}}")
+        elif name == "values":
+            parts.append(f"{dumps(name)}:{dumps(value)}")
+        else:
+            parts.append(f"{dumps(name)}:[\n" + ",\n".join(dumps(v) for v in value) + "\n]")
+    path = os.path.join(HERE, "tuning_table.json")
+    with open(path, "w") as f:
+        f.write("{\n" + ",\n".join(parts) + "\n}\n")
+    print("wrote", path)
+
+
 def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "tuning_table":   # make_golden.py tuning_table <dir of the libraries>
+        return write_tuning_table(sys.argv[2])
     kat = {"published": published_kats(), "build_pins": build_pins(), "large": large_vectors(),
            "load_block": glue_cases(), "f32_hazard_release": f32_hazard_release()}
     with open(os.path.join(HERE, "kat.json"), "w") as f:

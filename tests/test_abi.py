@@ -311,6 +311,37 @@ def test_tuning_api():
         shmr_amd.set_tuning(ptrs_direct=-7)
 
 
+@pytest.mark.parametrize("flavour", ["product", "tools"])
+def test_tuning_table_matches_the_record(flavour):
+    """Every knob's answers are the recorded ones (tests/golden/tuning_table.json,
+    recorded before the knobs became table rows): per key form and value the
+    status of set_tuning and what get_tuning then reads for each form, and the
+    describe strings at default tuning and under each kernel knob alone.
+    Exact, and no device is touched."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(ROOT, "tests", "golden", "make_golden.py"))
+    G = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(G)
+    with open(os.path.join(ROOT, "tests", "golden", "tuning_table.json")) as f:
+        table = json.load(f)
+    assert table["values"] == G.TUNING_VALUES
+    want = G.tuning_unpacked(table, flavour)
+    L = _native._load(flavour)
+    try:
+        got = G.tuning_record(L)
+    finally:
+        for name in G.TUNING_NAMES:
+            L.shmr_ec_set_tuning(name.encode(), G.TUNING_RESET.get(name, -2))
+    assert sorted(got["keys"]) == sorted(want["keys"]) and len(want["keys"]) == len(G.TUNING_NAMES)
+    for key in want["keys"]:
+        assert got["keys"][key] == want["keys"][key], key
+    assert sorted(got["describe"]) == sorted(want["describe"])
+    assert len(want["describe"]) == (1 + 2 * sum(len(v) for v in G.KERNEL_KNOBS.values()) if flavour == "tools" else 1)
+    for config in want["describe"]:
+        assert got["describe"][config] == want["describe"][config], config
+
+
 def test_auto_policy_variants_are_compiled():
     """Every shape the auto policy can pick maps to a compiled kernel."""
     for decode in (0, 1, 2, 3, 4):   # 3 / 4: the *_ptrs_dev calls
