@@ -20,6 +20,7 @@
 #include <map>
 #include <memory>
 #include <new>
+#include <numeric>
 #include <thread>
 #include <tuple>
 
@@ -638,6 +639,37 @@ struct VirtualBlock::State {
         }
         return read_slot_counted(fd, slot, S, o.pread_from_start, odd);
     }
+    // A flush whose encode failed after its data shard files went out: those
+    // hold the new bytes while the parity files hold the old parity, so the
+    // stripe is no codeword.  Make that detectable under every option set --
+    // every parity file unlinked (its handles closed; the next flush recreates
+    // it, ensure_fd): a later load fails to open it (reference rule) or, under
+    // missing_shard_is_erasure, counts it as an erasure, never as a present
+    // shard (a truncated file would be zero-padded and kept present when
+    // short_shard_is_erasure is off, block.rs:548-551, and a lost data shard
+    // then rebuilt from zeros) -- and leave the block dirty so the next flush
+    // re-encodes.  (The reference unwraps the encode before any write,
+    // block.rs:427.)
+    void drop_parity_files(size_t k, size_t nw, const ShmrFsConfig& cfg, bool fsync_dir) {
+        for (size_t i = k; i < nw; ++i) {
+            fs::path file;
+            if (!handles[i].first.resolve(cfg, &file, nullptr) && ::unlink(file.c_str()) == 0 &&
+                fsync_dir) {   // the unlink reaches the directory
+                const int dfd = ::open(file.parent_path().c_str(), O_RDONLY | O_DIRECTORY);
+                if (dfd >= 0) {
+                    (void)::fsync(dfd);
+                    ::close(dfd);
+                }
+            }
+            if (handles[i].second >= 0) ::close(handles[i].second);
+            handles[i].second = -1;
+            if (i < dfds.size()) {
+                if (dfds[i] >= 0) ::close(dfds[i]);
+                dfds[i] = -1;
+            }
+        }
+        should_flush.store(true);
+    }
     std::vector<int> dfds;   // O_DIRECT descriptors (direct_io), -1 unopened, -2 refused
     ~State() { close_handles(); }
 };
@@ -689,7 +721,82 @@ void shard_ptrs(BlockBuffer& buf, size_t n, size_t S, uint8_t** out) {
     for (size_t i = 0; i < n; ++i) out[i] = buf.data() + i * S;
 }
 
+// ReedSolomon::new for an Erasure topology (block.rs:405, :529), its calls on
+// GPU `device` (0: the default).  Null with *status set when either fails.
+std::unique_ptr<ReedSolomon> codec_for(const BlockTopology& t, int device, Status* status) {
+    EcStatus es;
+    auto r = ReedSolomon::create(t.data, t.parity, &es);
+    int rc = es.code;
+    if (r && device != 0) rc = shmr_ec_set_device(r->handle(), device);
+    if (rc == SHMR_EC_OK) return r;
+    *status = ec_error(rc);
+    return nullptr;
+}
+
+Status first_error(const std::vector<Status>& results) {
+    for (auto& r : results)
+        if (r) return r;
+    return std::nullopt;
+}
+
 }  // namespace
+
+// The shard reads of one Erasure block's load (block.rs:531-556): which shard
+// files are read (VfsOptions::read_needed_shards), what each read found, and
+// whether the block needs a reconstruct.  The caller holds the block's buffer
+// and handle locks.  read(i) touches only shard i's entries, so the reads of
+// one block, or of many blocks, may run in parallel.
+struct VirtualBlock::ShardLoad {
+    const VirtualBlock* b;
+    size_t S, k, n;
+    std::vector<int> fds;
+    std::vector<uint8_t*> slots;
+    std::vector<uint8_t> plan, present, odd;
+
+    // Sizes the block's buffer to n slots of S bytes and plans the reads.
+    ShardLoad(const VirtualBlock& blk, size_t shards)
+        : b(&blk), S(blk.shard_size()), k(blk.topology.data), n(shards), fds(n), slots(n), plan(n, kRead),
+          present(n, 0), odd(n, 0) {
+        State& st = *b->st_;
+        st.buffer.reserve(std::max<size_t>(b->size, n * S));
+        if (st.buffer.size() < b->size) st.buffer.set_len_uninit(b->size);   // every slot byte is overwritten
+        shard_ptrs(st.buffer, n, S, slots.data());
+        for (size_t i = 0; i < n; ++i) fds[i] = i < st.handles.size() ? st.handles[i].second : -1;
+        const VfsOptions& o = b->opt_;
+        if (!(o.read_needed_shards && o.pread_from_start && b->size <= k * S &&
+              plan_needed_reads(fds.data(), n, k, S, o.short_shard_is_erasure, plan.data())))
+            std::fill(plan.begin(), plan.end(), uint8_t(kRead));
+    }
+    // Shard i's part of the plan: read_to_end into its slot (Err -> None, block.rs:540-553).
+    void read(size_t i) {
+        if (plan[i] == kPresentUnread) present[i] = 1;
+        if (plan[i] != kRead || fds[i] < 0) return;
+        bool o = false;
+        if (b->st_->read_shard(i, fds[i], *b->cfg_, b->opt_, slots[i], S, &o) != 0) return;
+        present[i] = !(o && b->opt_.short_shard_is_erasure);
+        odd[i] = o;
+    }
+    // After the planned reads: if one of them failed or found another length,
+    // the shards counted present unread are to be read as well (returned).
+    std::vector<size_t> unread_after_failure() {
+        std::vector<size_t> rest;
+        bool failed = false;
+        for (size_t i = 0; i < n; ++i) failed |= plan[i] == kRead && (!present[i] || odd[i]);
+        for (size_t i = 0; failed && i < n; ++i)
+            if (plan[i] == kPresentUnread) {
+                plan[i] = kRead;
+                present[i] = 0;
+                rest.push_back(i);
+            }
+        return rest;
+    }
+    // Any shard absent or of another length: the block needs a reconstruct.
+    bool missing() const {
+        bool m = false;
+        for (size_t i = 0; i < n; ++i) m |= !present[i] || odd[i];
+        return m;
+    }
+};
 
 VirtualBlock::VirtualBlock() : st_(std::make_shared<State>()) {}
 
@@ -788,14 +895,10 @@ Status VirtualBlock::sync_data(bool force, int device, PhaseTimes* times) const 
     const size_t nh = st_->handles.size();
     std::vector<Status> res(nh);
     if (topology.kind == BlockTopology::Erasure) {
-        EcStatus es;
-        auto r = ReedSolomon::create(topology.data, topology.parity, &es);   // block.rs:405
-        if (!r) return ec_error(es.code);
-        if (device != 0) {
-            const int rc = shmr_ec_set_device(r->handle(), device);
-            if (rc != SHMR_EC_OK) return ec_error(rc);
-        }
-        const size_t S = shard_size();                                      // block.rs:406
+        Status err;
+        auto r = codec_for(topology, device, &err);   // block.rs:405
+        if (!r) return err;
+        const size_t S = shard_size();                // block.rs:406
         std::vector<uint8_t> tail;
         if (auto e = prepare_erasure(buffer, topology, S, opt_.release_u8_wrap, &tail)) return e;
         const size_t n = size_t(topology.data) + topology.parity;
@@ -807,7 +910,7 @@ Status VirtualBlock::sync_data(bool force, int device, PhaseTimes* times) const 
         // the parity files after the wait.  block.rs:436-439 writes all k+p.
         const double tc = times ? now_s() : 0;
         EcOp op;
-        es = r->encode_start(ptrs.data(), n, S, &op);
+        EcStatus es = r->encode_start(ptrs.data(), n, S, &op);
         if (es.ok()) {
             const size_t k = topology.data, nw = std::min(n, nh);
             const double tw = times ? now_s() : 0;
@@ -815,37 +918,7 @@ Status VirtualBlock::sync_data(bool force, int device, PhaseTimes* times) const 
             const double tw2 = times ? now_s() : 0;
             es = op.wait();
             if (es.ok() && opt_.fault_encode_wait) es = EcStatus{SHMR_EC_DEVICE_ERROR};   // test hook
-            if (!es.ok()) {
-                // The data shard files already hold the new bytes while the parity
-                // files hold the old parity: the stripe is no codeword.  Make that
-                // detectable under every option set -- every parity file unlinked
-                // (its handles closed; the next flush recreates it, ensure_fd): a
-                // later load fails to open it (reference rule) or, under
-                // missing_shard_is_erasure, counts it as an erasure, never as a
-                // present shard (a truncated file would be zero-padded and kept
-                // present when short_shard_is_erasure is off, block.rs:548-551,
-                // and a lost data shard then rebuilt from zeros) -- and leave the
-                // block dirty so the next flush re-encodes.  (The reference
-                // unwraps the encode before any write, block.rs:427.)
-                for (size_t i = k; i < nw; ++i) {
-                    fs::path file;
-                    if (!st_->handles[i].first.resolve(*cfg_, &file, nullptr) && ::unlink(file.c_str()) == 0 &&
-                        opt_.fsync_shards) {   // the unlink reaches the directory
-                        const int dfd = ::open(file.parent_path().c_str(), O_RDONLY | O_DIRECTORY);
-                        if (dfd >= 0) {
-                            (void)::fsync(dfd);
-                            ::close(dfd);
-                        }
-                    }
-                    if (st_->handles[i].second >= 0) ::close(st_->handles[i].second);
-                    st_->handles[i].second = -1;
-                    if (i < st_->dfds.size()) {
-                        if (st_->dfds[i] >= 0) ::close(st_->dfds[i]);
-                        st_->dfds[i] = -1;
-                    }
-                }
-                st_->should_flush.store(true);
-            }
+            if (!es.ok()) st_->drop_parity_files(k, nw, *cfg_, opt_.fsync_shards);
             if (times) times->codec_s += now_s() - tc - (tw2 - tw), times->io_s += tw2 - tw;
             if (es.ok() && nw > k) {
                 const double tp = times ? now_s() : 0;
@@ -856,11 +929,8 @@ Status VirtualBlock::sync_data(bool force, int device, PhaseTimes* times) const 
                 if (times) times->io_s += now_s() - tp;
             }
         }
-        if (!es.ok()) {
-            restore_tail(buffer, topology, S, tail);
-            return ec_error(es.code);
-        }
         restore_tail(buffer, topology, S, tail);
+        if (!es.ok()) return ec_error(es.code);
     } else {
         const size_t copies = topology.kind == BlockTopology::Single ? 1 : std::min<size_t>(topology.n, nh);
         parallel_for(copies, 16, [&](size_t i) {
@@ -868,8 +938,7 @@ Status VirtualBlock::sync_data(bool force, int device, PhaseTimes* times) const 
             if (!res[i]) res[i] = write_path(st_->handles[i].second, buffer.data(), buffer.size(), opt_.fsync_shards);
         });
     }
-    for (auto& e : res)
-        if (e) return e;
+    if (auto e = first_error(res)) return e;
     st_->should_flush.store(false);
     return std::nullopt;
 }
@@ -915,65 +984,30 @@ Status VirtualBlock::load_block(bool* reconstructed, int device, PhaseTimes* tim
         return fs_error(ENOSYS);   // todo!("Implement Mirrored Read") in the reference
     } else {
         if (topology.version != 1) return fs_error(ENOSYS);   // unimplemented!()
-        EcStatus es;
-        auto r = ReedSolomon::create(topology.data, topology.parity, &es);
-        if (!r) return ec_error(es.code);
-        if (device != 0) {
-            const int rc = shmr_ec_set_device(r->handle(), device);
-            if (rc != SHMR_EC_OK) return ec_error(rc);
-        }
-        const size_t S = shard_size();
-        const size_t n = st_->handles.size();
-        buffer.reserve(std::max<size_t>(size, n * S));
-        if (buffer.size() < size) buffer.set_len_uninit(size);   // every slot byte is overwritten below
-        std::vector<uint8_t*> ptrs(n);
-        shard_ptrs(buffer, n, S, ptrs.data());
-        std::vector<uint8_t> present(n, 0), odd(n, 0), plan(n, kRead);
-        std::vector<int> fds(n);
-        for (size_t i = 0; i < n; ++i) fds[i] = st_->handles[i].second;
-        const bool planned = opt_.read_needed_shards && opt_.pread_from_start && size <= size_t(topology.data) * S &&
-                             plan_needed_reads(fds.data(), n, topology.data, S, opt_.short_shard_is_erasure, plan.data());
-        if (!planned) std::fill(plan.begin(), plan.end(), uint8_t(kRead));
-        auto read_one = [&](size_t i) {
-            bool o = false;
-            if (fds[i] >= 0 && st_->read_shard(i, fds[i], *cfg_, opt_, ptrs[i], S, &o) == 0) {   // Err -> None
-                present[i] = !(o && opt_.short_shard_is_erasure);
-                odd[i] = o;
-            }
-        };
+        Status err;
+        auto r = codec_for(topology, device, &err);
+        if (!r) return err;
+        ShardLoad ld(*this, st_->handles.size());
         const double tr = times ? now_s() : 0;
-        parallel_for(n, 16, [&](size_t i) {
-            if (plan[i] == kRead) read_one(i);
-            else if (plan[i] == kPresentUnread) present[i] = 1;
-        });
-        if (planned) {   // a planned read failed or changed length: read the rest as well
-            bool redo = false;
-            for (size_t i = 0; i < n; ++i) redo |= plan[i] == kRead && (!present[i] || odd[i]);
-            if (redo)
-                parallel_for(n, 16, [&](size_t i) {
-                    if (plan[i] == kPresentUnread) {
-                        present[i] = 0;
-                        read_one(i);
-                    }
-                });
-        }
+        parallel_for(ld.n, 16, [&](size_t i) { ld.read(i); });
+        const std::vector<size_t> rest = ld.unread_after_failure();
+        parallel_for(rest.size(), 16, [&](size_t j) { ld.read(rest[j]); });
         if (times) times->io_s += now_s() - tr;
-        bool missing = false;
-        for (size_t i = 0; i < n; ++i) missing |= !present[i] || odd[i];
-        if (missing) {
+        if (ld.missing()) {
             const double tc = times ? now_s() : 0;
             double td = 0;
+            EcStatus es;
             if (during && *during) {   // copies of the present shards overlap the GPU work
                 EcOp op;
-                es = r->reconstruct_start(ptrs.data(), present.data(), n, S, false, &op);   // block.rs:560
+                es = r->reconstruct_start(ld.slots.data(), ld.present.data(), ld.n, ld.S, false, &op);   // block.rs:560
                 if (es.ok()) {
                     const double t1 = now_s();
-                    (*during)(present.data());
+                    (*during)(ld.present.data());
                     td = now_s() - t1;
                     es = op.wait();
                 }
             } else {
-                es = r->reconstruct_in_place(ptrs.data(), present.data(), n, S, false);   // block.rs:560 (unwrap)
+                es = r->reconstruct_in_place(ld.slots.data(), ld.present.data(), ld.n, ld.S, false);   // block.rs:560 (unwrap)
             }
             if (times) times->codec_s += now_s() - tc - td, times->overlap_s += td;
             if (!es.ok()) return ec_error(es.code);
@@ -1080,11 +1114,22 @@ std::vector<size_t> VirtualFile::blocks_for_range(uint64_t pos, size_t len) cons
 namespace {
 
 // A run of consecutive chunks inside one block, copied as one memcpy.
-struct ReadRun {
+struct ChunkRun {
     size_t blk;
     uint64_t block_pos;
     size_t off, len;
 };
+
+// The run that starts at chunk c of a read or write of `len` bytes whose
+// first `done` bytes are planned: every chunk up to end_chunk that lies in
+// c's block (*chunks of them), `len` bytes at most in all.
+ChunkRun run_at(uint64_t chunk_size, uint64_t block_size, uint64_t c, uint64_t end_chunk, size_t done, size_t len,
+                uint64_t* chunks) {
+    const uint64_t block_pos = c * chunk_size % block_size;
+    *chunks = std::min<uint64_t>(end_chunk - c + 1, (block_size - block_pos + chunk_size - 1) / chunk_size);
+    const size_t want = size_t(std::min<uint64_t>(uint64_t(done) + *chunks * chunk_size, len)) - done;
+    return {size_t(c * chunk_size / block_size), block_pos, done, want};
+}
 
 }  // namespace
 
@@ -1094,24 +1139,20 @@ struct ReadRun {
 // count) at a known offset; planning stops at the first run that could come
 // up short, and *c / *done say where the reference's chunk loop takes over.
 template <class Buffered>
-static std::vector<ReadRun> plan_read_runs(const std::vector<VirtualBlock>& blocks, uint64_t chunk_size,
+static std::vector<ChunkRun> plan_read_runs(const std::vector<VirtualBlock>& blocks, uint64_t chunk_size,
                                            uint64_t block_size, uint64_t pos, size_t len, Buffered buffered,
                                            uint64_t* c_out, size_t* done_out) {
     const uint64_t start_chunk = pos / chunk_size;
     const uint64_t end_chunk = len / chunk_size + start_chunk;
-    std::vector<ReadRun> runs;
+    std::vector<ChunkRun> runs;
     uint64_t c = start_chunk;
     size_t done = 0;
-    for (; c <= end_chunk;) {
-        const uint64_t block_idx = c * chunk_size / block_size;
-        const uint64_t block_pos = c * chunk_size % block_size;
-        if (block_idx >= blocks.size()) break;
-        const uint64_t run = std::min<uint64_t>(end_chunk - c + 1, (block_size - block_pos + chunk_size - 1) / chunk_size);
-        const size_t want = size_t(std::min<uint64_t>(uint64_t(done) + run * chunk_size, len)) - done;
-        if (want > 0 && buffered(size_t(block_idx)) < block_pos + want) break;
-        if (want > 0) runs.push_back({size_t(block_idx), block_pos, done, want});
-        done += want;
-        c += run;
+    for (uint64_t chunks = 0; c <= end_chunk; c += chunks) {
+        const ChunkRun r = run_at(chunk_size, block_size, c, end_chunk, done, len, &chunks);
+        if (r.blk >= blocks.size()) break;
+        if (r.len > 0 && buffered(r.blk) < r.block_pos + r.len) break;
+        if (r.len > 0) runs.push_back(r);
+        done += r.len;
     }
     *c_out = c;
     *done_out = done;
@@ -1131,7 +1172,7 @@ Status VirtualFile::read(uint64_t pos, uint8_t* buf, size_t len, size_t* nread) 
     // is loaded, while later batches are still reading / reconstructing.
     uint64_t c_early = 0;
     size_t done_early = 0;
-    const std::vector<ReadRun> early = plan_read_runs(
+    const std::vector<ChunkRun> early = plan_read_runs(
         blocks, chunk_size, block_size, pos, len,
         [&](size_t bi) -> uint64_t {
             const VirtualBlock& b = blocks[bi];
@@ -1155,7 +1196,7 @@ Status VirtualFile::read(uint64_t pos, uint8_t* buf, size_t len, size_t* nread) 
         const uint64_t S = b.shard_size(), k = b.topology.data;
         const auto& data = b.st_->buffer;   // locked by the load task (this thread)
         for (size_t q : it->second) {
-            const ReadRun& r = early[q];
+            const ChunkRun& r = early[q];
             if (data.size() < r.block_pos + r.len || S == 0) continue;
             for (uint64_t p0 = r.block_pos, end = r.block_pos + r.len; p0 < end;) {
                 const uint64_t s = p0 / S, p1 = std::min(end, (s + 1) * S);
@@ -1175,7 +1216,7 @@ Status VirtualFile::read(uint64_t pos, uint8_t* buf, size_t len, size_t* nread) 
         // load_blocks holds these blocks' locks until this returns; read their
         // buffers directly (VirtualBlock::read would take the lock again)
         parallel_for(todo.size(), todo.size() > 4 ? 8 : 1, [&](size_t q) {
-            const ReadRun& r = early[todo[q]];
+            const ChunkRun& r = early[todo[q]];
             const auto& data = blocks[r.blk].st_->buffer;
             if (data.size() < r.block_pos + r.len) return;   // not as planned: the plan below copies it
             if (split[todo[q]]) {
@@ -1190,13 +1231,13 @@ Status VirtualFile::read(uint64_t pos, uint8_t* buf, size_t len, size_t* nread) 
     if (auto e = load_blocks(blocks_for_range(pos, len), on_batch, during_rebuild)) return e;
     uint64_t c = 0;
     size_t done = 0;
-    std::vector<ReadRun> runs = plan_read_runs(blocks, chunk_size, block_size, pos, len,
+    std::vector<ChunkRun> runs = plan_read_runs(blocks, chunk_size, block_size, pos, len,
                                                [&](size_t bi) -> uint64_t { return blocks[bi].buffered_len(); },
                                                &c, &done);
     {   // runs already copied during the load (same run, same bytes) are skipped
-        std::vector<ReadRun> left;
+        std::vector<ChunkRun> left;
         size_t e = 0;
-        for (const ReadRun& r : runs) {
+        for (const ChunkRun& r : runs) {
             while (e < early.size() && early[e].off < r.off) ++e;
             const bool same = e < early.size() && copied[e] && early[e].blk == r.blk &&
                               early[e].block_pos == r.block_pos && early[e].off == r.off && early[e].len == r.len;
@@ -1210,8 +1251,7 @@ Status VirtualFile::read(uint64_t pos, uint8_t* buf, size_t len, size_t* nread) 
         size_t n = 0;
         res[i] = blocks[runs[i].blk].read(runs[i].block_pos, buf + runs[i].off, runs[i].len, &n);
     });
-    for (auto& e : res)
-        if (e) return e;
+    if (auto e = first_error(res)) return e;
     for (; c <= end_chunk; ++c) {   // the reference's loop for the rest
         const uint64_t block_idx = c * chunk_size / block_size;
         const uint64_t block_pos = c * chunk_size % block_size;
@@ -1238,33 +1278,23 @@ Status VirtualFile::write(uint64_t pos, const uint8_t* buf, size_t len, size_t* 
     // write each, done in parallel.  From the first run that does not fit,
     // the rest goes chunk by chunk so OutOfSpace leaves exactly the bytes the
     // reference's loop leaves.
-    struct Run {
-        size_t blk;
-        uint64_t block_pos;
-        size_t off, len;
-    };
-    std::vector<Run> runs;
+    std::vector<ChunkRun> runs;
     uint64_t c = start_chunk;
     size_t written = 0;
-    for (; c <= end_chunk;) {
+    for (uint64_t chunks = 0; c <= end_chunk; c += chunks) {
         while (blocks.size() * chk_per_blk <= c)
             if (auto e = allocate_block()) return e;
-        const uint64_t block_idx = c * chunk_size / block_size;
-        const uint64_t block_pos = c * chunk_size % block_size;
-        const uint64_t run = std::min<uint64_t>(end_chunk - c + 1, (block_size - block_pos + chunk_size - 1) / chunk_size);
-        const size_t want = size_t(std::min<uint64_t>(uint64_t(written) + run * chunk_size, len)) - written;
-        if (block_pos + want > blocks[block_idx].size) break;
-        runs.push_back({size_t(block_idx), block_pos, written, want});
-        written += want;
-        c += run;
+        const ChunkRun r = run_at(chunk_size, block_size, c, end_chunk, written, len, &chunks);
+        if (r.block_pos + r.len > blocks[r.blk].size) break;
+        runs.push_back(r);
+        written += r.len;
     }
     std::vector<Status> res(runs.size());
     parallel_for(runs.size(), runs.size() > 4 ? 8 : 1, [&](size_t i) {
         size_t n = 0;
         res[i] = blocks[runs[i].blk].write(runs[i].block_pos, buf + runs[i].off, runs[i].len, &n);
     });
-    for (auto& e : res)
-        if (e) return e;
+    if (auto e = first_error(res)) return e;
     for (; c <= end_chunk; ++c) {   // the reference's loop for the rest
         while (blocks.size() * chk_per_blk <= c)
             if (auto e = allocate_block()) return e;
@@ -1280,110 +1310,168 @@ Status VirtualFile::write(uint64_t pos, const uint8_t* buf, size_t len, size_t* 
     return std::nullopt;
 }
 
+// ---------------------------------------------------------------------------
+// VirtualFile flush and load.  Mapped Block-Cache buffers with the auto batch
+// run one task per block (flush_per_block, load_per_block); everything else
+// runs pipelined batches per (k, p, S) (flush_batched, load_batched).
+// ---------------------------------------------------------------------------
+struct VirtualFile::Group {
+    unsigned k = 0, p = 0;
+    size_t S = 0;
+    std::vector<size_t> members;   // block indices
+    size_t n() const { return size_t(k) + p; }
+};
+
+// Members [b, e) of a group, coded in one call; `first` counts the members of
+// all batches before it (batches follow each other in group, then member order).
+struct VirtualFile::Batch {
+    const Group* g;
+    size_t b, e, first;
+};
+
 namespace {
 
 // Locks held over a batch: every block's buffer lock, then its handle lock,
 // in block order (the order VirtualBlock::sync_data / load_block take them).
-struct BatchLocks {
-    std::vector<std::unique_lock<std::mutex>> held;
-};
+using BatchLocks = std::vector<std::unique_lock<std::mutex>>;
 
-struct Group {
-    unsigned k = 0, p = 0;
-    size_t S = 0;
-    std::vector<size_t> members;   // block indices
-};
+// One task per block of `todo` on the worker pool (mod.rs:93-96's par_iter),
+// blocks round-robin over the GPUs.  task(i, device, &phase_times, &copy_s)
+// flushes or loads block i and says whether the codec ran for it: that count
+// goes to stats->blocks, the tasks' thread time to stats->task_* (the file
+// I/O to *io_field).
+template <class Task>
+void run_block_tasks(const std::vector<size_t>& todo, size_t width, const std::vector<int>& devices, IoStats* stats,
+                     double IoStats::*io_field, Task task) {
+    const size_t nd = std::max<size_t>(1, devices.size());
+    std::atomic<size_t> coded{0};
+    std::mutex tmu;
+    parallel_for(todo.size(), width, [&](size_t q) {
+        const size_t i = todo[q];
+        const double ts = now_s();
+        PhaseTimes pt;
+        double copy_s = 0;
+        if (task(i, devices.empty() ? 0 : devices[i % nd], &pt, &copy_s)) ++coded;
+        std::lock_guard<std::mutex> lock(tmu);
+        stats->*io_field += pt.io_s;
+        stats->task_codec_s += pt.codec_s;
+        stats->task_copy_s += copy_s;
+        stats->task_overlap_s += pt.overlap_s;
+        stats->task_total_s += now_s() - ts;
+        ++stats->tasks;
+    });
+    stats->blocks = coded.load();
+}
 
 }  // namespace
 
-// mod.rs:91-103, MI355X-batched.
-Status VirtualFile::sync_data(bool force) {
-    last_sync = IoStats{};
-    const double t0 = now_s();
-    std::vector<Status> results(blocks.size());
-    if (opt_.pinned_buffers && pipeline_batch_bytes == kAutoBatch) {
-        // one flush task per block (mod.rs:93-96's par_iter), blocks round-robin over the GPUs
-        const size_t nd = std::max<size_t>(1, devices.size());
-        std::atomic<size_t> coded{0};
-        std::mutex tmu;
-        parallel_for(blocks.size(), per_block_tasks, [&](size_t i) {
-            const VirtualBlock& b = blocks[i];
-            const bool dirty = force || b.st_->should_flush.load();
-            const double ts = now_s();
-            PhaseTimes pt;
-            results[i] = b.sync_data(force, devices.empty() ? 0 : devices[i % nd], &pt);
-            if (!results[i] && dirty && b.topology.kind == BlockTopology::Erasure) ++coded;
-            std::lock_guard<std::mutex> lock(tmu);
-            last_sync.task_write_s += pt.io_s;
-            last_sync.task_codec_s += pt.codec_s;
-            last_sync.task_total_s += now_s() - ts;
-            ++last_sync.tasks;
-        });
-        last_sync.blocks = coded.load();
-        last_sync.total_s = now_s() - t0;
-        for (auto& r : results)
-            if (r) return r;
-        return std::nullopt;
-    }
-    std::map<std::tuple<unsigned, unsigned, size_t>, Group> groups;
-    std::vector<size_t> others;
-    for (size_t i = 0; i < blocks.size(); ++i) {
+// The blocks of `indices` that `grouped` accepts, by (k, p, S); the others'
+// indices go to *others.
+std::vector<VirtualFile::Group> VirtualFile::erasure_groups(const std::vector<size_t>& indices,
+                                                            const std::function<bool(const VirtualBlock&)>& grouped,
+                                                            std::vector<size_t>* others) const {
+    std::map<std::tuple<unsigned, unsigned, size_t>, Group> by_code;
+    for (size_t i : indices) {
         const VirtualBlock& b = blocks[i];
-        if (b.topology.kind != BlockTopology::Erasure) {
-            others.push_back(i);
+        if (!grouped(b)) {
+            others->push_back(i);
             continue;
         }
-        if (!force && !b.st_->should_flush.load()) continue;
         const size_t S = b.shard_size();
-        Group& g = groups[{b.topology.data, b.topology.parity, S}];
+        Group& g = by_code[{b.topology.data, b.topology.parity, S}];
         g.k = b.topology.data;
         g.p = b.topology.parity;
         g.S = S;
         g.members.push_back(i);
     }
-    {   // open missing shard handles of every grouped block in parallel
-        // (hundreds of open() calls per flush/load; block.rs:455-493 per block)
-        std::vector<size_t> need;
-        for (auto& kv : groups)
-            for (size_t i : kv.second.members)
-                if (!blocks[i].st_->shard_loaded.load()) need.push_back(i);
-        parallel_for(need.size(), 16, [&](size_t j) { results[need[j]] = blocks[need[j]].open_handles(); });
+    std::vector<Group> groups;
+    for (auto& kv : by_code) groups.push_back(std::move(kv.second));
+    return groups;
+}
+
+// Opens the shard handles of every grouped block that has none, in parallel
+// (hundreds of open() calls per flush / load; block.rs:455-493 per block).
+void VirtualFile::open_missing_handles(const std::vector<Group>& groups, std::vector<Status>* results) const {
+    std::vector<size_t> need;
+    for (const Group& g : groups)
+        for (size_t i : g.members)
+            if (!blocks[i].st_->shard_loaded.load()) need.push_back(i);
+    parallel_for(need.size(), 16, [&](size_t j) { (*results)[need[j]] = blocks[need[j]].open_handles(); });
+}
+
+// Batches of about batch_bytes of data per (k, p, S), at least one block each;
+// 0: one batch per group.  The codec call of one batch overlaps the shard-file
+// I/O of its neighbour.
+std::vector<VirtualFile::Batch> VirtualFile::split_batches(const std::vector<Group>& groups, size_t batch_bytes) {
+    std::vector<Batch> batches;
+    size_t first = 0;
+    for (const Group& g : groups) {
+        const size_t nm = g.members.size();
+        const size_t per = batch_bytes == 0 ? nm : std::max<size_t>(1, batch_bytes / std::max<size_t>(1, size_t(g.k) * g.S));
+        for (size_t b = 0; b < nm; b += per) batches.push_back({&g, b, std::min(nm, b + per), first + b});
+        first += nm;
     }
+    return batches;
+}
+
+// mod.rs:91-103, MI355X-batched.
+Status VirtualFile::sync_data(bool force) {
+    last_sync = IoStats{};
+    return opt_.pinned_buffers && pipeline_batch_bytes == kAutoBatch ? flush_per_block(force) : flush_batched(force);
+}
+
+Status VirtualFile::flush_per_block(bool force) {
+    const double t0 = now_s();
+    std::vector<Status> results(blocks.size());
+    std::vector<size_t> all(blocks.size());
+    std::iota(all.begin(), all.end(), size_t(0));
+    run_block_tasks(all, per_block_tasks, devices, &last_sync, &IoStats::task_write_s,
+                    [&](size_t i, int device, PhaseTimes* pt, double*) {
+                        const VirtualBlock& b = blocks[i];
+                        const bool dirty = force || b.st_->should_flush.load();
+                        results[i] = b.sync_data(force, device, pt);
+                        return !results[i] && dirty && b.topology.kind == BlockTopology::Erasure;
+                    });
+    last_sync.total_s = now_s() - t0;
+    return first_error(results);
+}
+
+Status VirtualFile::flush_batched(bool force) {
+    const double t0 = now_s();
+    std::vector<Status> results(blocks.size());
+    std::vector<size_t> all(blocks.size()), others;
+    std::iota(all.begin(), all.end(), size_t(0));
+    // Dirty (or forced) Erasure blocks of any version are batched; every other
+    // block flushes itself at the end (a clean one returns at once).
+    auto dirty_erasure = [&](const VirtualBlock& b) {
+        return b.topology.kind == BlockTopology::Erasure && (force || b.st_->should_flush.load());
+    };
+    std::vector<Group> groups = erasure_groups(all, dirty_erasure, &others);
+    open_missing_handles(groups, &results);
     BatchLocks locks;
     std::vector<std::vector<uint8_t>> tails(blocks.size());   // release_u8_wrap only
-    for (auto& kv : groups) {
-        Group& g = kv.second;
+    for (Group& g : groups) {
         std::vector<size_t> live;
         for (size_t i : g.members) {
             if (results[i]) continue;   // open failed
             VirtualBlock& b = blocks[i];
-            locks.held.emplace_back(b.st_->buf_mu);
+            locks.emplace_back(b.st_->buf_mu);
             if (b.st_->buffer.empty()) continue;   // block.rs:389-391: nothing to write
             if ((results[i] = prepare_erasure(b.st_->buffer, b.topology, g.S, b.opt_.release_u8_wrap, &tails[i])))
                 continue;
-            locks.held.emplace_back(b.st_->handles_mu);
+            locks.emplace_back(b.st_->handles_mu);
             live.push_back(i);
         }
         g.members.swap(live);
     }
     last_sync.prepare_s = now_s() - t0;
-    // Batches of ~64 MiB of data per (k, p, S): the encode of batch b+1 (one
-    // pipelined multi-GPU call) overlaps the shard-file writes of batch b
-    // (every (block, shard) file of the batch in parallel, block.rs:436-439).
-    struct Batch {
-        const Group* g;
-        size_t b, e;   // members [b, e)
-    };
-    std::vector<Batch> batches;
-    for (auto& kv : groups) {
-        const Group& g = kv.second;
-        const size_t bb = batch_bytes(false);
-        const size_t per = bb == 0 ? g.members.size() : std::max<size_t>(1, bb / std::max<size_t>(1, size_t(g.k) * g.S));
-        for (size_t b = 0; b < g.members.size(); b += per) batches.push_back({&g, b, std::min(g.members.size(), b + per)});
-    }
+    // The encode of batch b+1 (one pipelined multi-GPU call) overlaps the
+    // shard-file writes of batch b (every (block, shard) file of the batch in
+    // parallel, block.rs:436-439).
+    const std::vector<Batch> batches = split_batches(groups, batch_bytes(false));
     auto encode_batch = [&](const Batch& bt) {
         const Group& g = *bt.g;
-        const size_t n = size_t(g.k) + g.p, nb = bt.e - bt.b;
+        const size_t n = g.n(), nb = bt.e - bt.b;
         std::vector<uint8_t*> ptrs(nb * n);
         for (size_t j = 0; j < nb; ++j) shard_ptrs(blocks[g.members[bt.b + j]].st_->buffer, n, g.S, &ptrs[j * n]);
         EcStatus es;
@@ -1403,7 +1491,7 @@ Status VirtualFile::sync_data(bool force) {
         for (size_t j = bt.b; j < bt.e; ++j) {
             const size_t i = g.members[j];
             if (results[i]) continue;
-            for (size_t sh = 0; sh < size_t(g.k) + g.p && sh < blocks[i].st_->handles.size(); ++sh) tasks.push_back({i, sh});
+            for (size_t sh = 0; sh < g.n() && sh < blocks[i].st_->handles.size(); ++sh) tasks.push_back({i, sh});
         }
         std::vector<Status> task_res(tasks.size());
         parallel_for(tasks.size(), 32, [&](size_t t) {
@@ -1437,191 +1525,96 @@ Status VirtualFile::sync_data(bool force) {
     if (writer.valid()) writer.get();
     last_sync.io_s = io_busy;
     last_sync.total_s = now_s() - t1;
-    locks.held.clear();
+    locks.clear();
     parallel_for(others.size(), 16, [&](size_t j) { results[others[j]] = blocks[others[j]].sync_data(force); });
-    for (auto& r : results)
-        if (r) return r;
-    return std::nullopt;
+    return first_error(results);
 }
 
 // Batched load_block (block.rs:496-584) over several blocks: the same rules
 // per block, one reconstruct call per (k, p, S) for the blocks with erasures.
-Status VirtualFile::load_blocks(const std::vector<size_t>& block_indices,
-                                const std::function<void(const std::vector<size_t>&)>& on_batch,
+Status VirtualFile::load_blocks(const std::vector<size_t>& block_indices, const OnBatch& on_batch,
                                 const DuringRebuild& during_rebuild) {
     last_load = IoStats{};
-    const double t0 = now_s();
-    std::vector<Status> results(blocks.size());
-    if (opt_.pinned_buffers && pipeline_batch_bytes == kAutoBatch) {
-        // one load task per block (block.rs:496-584 each), blocks round-robin over the GPUs
-        std::vector<size_t> todo;
-        for (size_t i : block_indices) {
-            if (i >= blocks.size()) return ShmrError{ShmrError::BlockIndexOutOfBounds};
-            if (!blocks[i].st_->buffer_loaded.load()) todo.push_back(i);
-        }
-        const size_t nd = std::max<size_t>(1, devices.size());
-        std::atomic<size_t> rebuilt{0};
-        std::mutex tmu;
-        parallel_for(todo.size(), per_block_read_tasks, [&](size_t q) {
-            const size_t i = todo[q];
-            const VirtualBlock& b = blocks[i];
-            bool rec = false;
-            const double ts = now_s();
-            PhaseTimes pt;
-            std::function<void(const uint8_t*)> during;
-            if (during_rebuild) during = [&, i](const uint8_t* present) { during_rebuild(i, present); };
-            results[i] = b.load_block(&rec, devices.empty() ? 0 : devices[i % nd], &pt, &during);
-            if (rec) ++rebuilt;
-            double copy_s = 0;
-            if (!results[i] && on_batch && b.topology.kind == BlockTopology::Erasure) {
-                std::lock_guard<std::mutex> lock(b.st_->buf_mu);   // on_batch reads the buffer unlocked
-                const double tc = now_s();
-                on_batch(std::vector<size_t>{i});
-                copy_s = now_s() - tc;
-            }
-            std::lock_guard<std::mutex> lock(tmu);
-            last_load.task_read_s += pt.io_s;
-            last_load.task_codec_s += pt.codec_s;
-            last_load.task_copy_s += copy_s;
-            last_load.task_overlap_s += pt.overlap_s;
-            last_load.task_total_s += now_s() - ts;
-            ++last_load.tasks;
-        });
-        last_load.blocks = rebuilt.load();
-        last_load.total_s = now_s() - t0;
-        for (auto& r : results)
-            if (r) return r;
-        return std::nullopt;
-    }
-    std::map<std::tuple<unsigned, unsigned, size_t>, Group> groups;
-    std::vector<size_t> others;
+    std::vector<size_t> todo;
     for (size_t i : block_indices) {
         if (i >= blocks.size()) return ShmrError{ShmrError::BlockIndexOutOfBounds};
-        const VirtualBlock& b = blocks[i];
-        if (b.st_->buffer_loaded.load()) continue;
-        if (b.topology.kind != BlockTopology::Erasure || b.topology.version != 1) {
-            others.push_back(i);   // Single, Mirror (ENOSYS) and unknown versions: per block
-            continue;
-        }
-        const size_t S = b.shard_size();
-        Group& g = groups[{b.topology.data, b.topology.parity, S}];
-        g.k = b.topology.data;
-        g.p = b.topology.parity;
-        g.S = S;
-        g.members.push_back(i);
+        if (!blocks[i].st_->buffer_loaded.load()) todo.push_back(i);
     }
-    {   // open missing shard handles of every grouped block in parallel
-        // (hundreds of open() calls per flush/load; block.rs:455-493 per block)
-        std::vector<size_t> need;
-        for (auto& kv : groups)
-            for (size_t i : kv.second.members)
-                if (!blocks[i].st_->shard_loaded.load()) need.push_back(i);
-        parallel_for(need.size(), 16, [&](size_t j) { results[need[j]] = blocks[need[j]].open_handles(); });
-    }
-    for (auto& kv : groups) {   // blocks whose handles failed to open keep their error
-        auto& m = kv.second.members;
+    return opt_.pinned_buffers && pipeline_batch_bytes == kAutoBatch ? load_per_block(todo, on_batch, during_rebuild)
+                                                                     : load_batched(todo, on_batch);
+}
+
+// One load task per block (block.rs:496-584 each).
+Status VirtualFile::load_per_block(const std::vector<size_t>& todo, const OnBatch& on_batch,
+                                   const DuringRebuild& during_rebuild) {
+    const double t0 = now_s();
+    std::vector<Status> results(blocks.size());
+    run_block_tasks(todo, per_block_read_tasks, devices, &last_load, &IoStats::task_read_s,
+                    [&](size_t i, int device, PhaseTimes* pt, double* copy_s) {
+                        const VirtualBlock& b = blocks[i];
+                        bool rec = false;
+                        std::function<void(const uint8_t*)> during;
+                        if (during_rebuild) during = [&, i](const uint8_t* present) { during_rebuild(i, present); };
+                        results[i] = b.load_block(&rec, device, pt, &during);
+                        if (!results[i] && on_batch && b.topology.kind == BlockTopology::Erasure) {
+                            std::lock_guard<std::mutex> lock(b.st_->buf_mu);   // on_batch reads the buffer unlocked
+                            const double tc = now_s();
+                            on_batch(std::vector<size_t>{i});
+                            *copy_s = now_s() - tc;
+                        }
+                        return rec;
+                    });
+    last_load.total_s = now_s() - t0;
+    return first_error(results);
+}
+
+Status VirtualFile::load_batched(const std::vector<size_t>& todo, const OnBatch& on_batch) {
+    const double t0 = now_s();
+    std::vector<Status> results(blocks.size());
+    std::vector<size_t> others;   // Single, Mirror (ENOSYS) and unknown versions: per block, at the end
+    auto erasure_v1 = [](const VirtualBlock& b) {
+        return b.topology.kind == BlockTopology::Erasure && b.topology.version == 1;
+    };
+    std::vector<Group> groups = erasure_groups(todo, erasure_v1, &others);
+    open_missing_handles(groups, &results);
+    for (Group& g : groups) {   // blocks whose handles failed to open keep their error
+        auto& m = g.members;
         m.erase(std::remove_if(m.begin(), m.end(), [&](size_t i) { return bool(results[i]); }), m.end());
     }
     BatchLocks locks;
-    struct Task {
-        size_t blk, shard, S;
-        uint8_t* slot;
-        int fd;
-        uint8_t plan;
-    };
-    std::vector<Task> tasks;
-    std::map<size_t, size_t> first_task;   // block -> index of its shard 0 task
-    for (auto& kv : groups) {
-        Group& g = kv.second;
-        const size_t n = size_t(g.k) + g.p;
+    std::vector<VirtualBlock::ShardLoad> loads;   // in group, then member order: Batch::first indexes it
+    for (const Group& g : groups)
         for (size_t i : g.members) {
-            auto& st = *blocks[i].st_;
-            locks.held.emplace_back(st.buf_mu);
-            locks.held.emplace_back(st.handles_mu);
-            st.buffer.reserve(std::max<size_t>(blocks[i].size, n * g.S));
-            if (st.buffer.size() < blocks[i].size) st.buffer.set_len_uninit(blocks[i].size);   // slots overwritten
-            first_task[i] = tasks.size();
-            for (size_t s = 0; s < n; ++s)
-                tasks.push_back({i, s, g.S, st.buffer.data() + s * g.S, s < st.handles.size() ? st.handles[s].second : -1,
-                                 uint8_t(kRead)});
-            const VfsOptions& o = blocks[i].opt_;
-            if (o.read_needed_shards && o.pread_from_start && blocks[i].size <= size_t(g.k) * g.S) {
-                std::vector<int> fds(n);
-                std::vector<uint8_t> plan(n);
-                for (size_t s = 0; s < n; ++s) fds[s] = tasks[first_task[i] + s].fd;
-                if (plan_needed_reads(fds.data(), n, g.k, g.S, o.short_shard_is_erasure, plan.data()))
-                    for (size_t s = 0; s < n; ++s) tasks[first_task[i] + s].plan = plan[s];
-            }
+            locks.emplace_back(blocks[i].st_->buf_mu);
+            locks.emplace_back(blocks[i].st_->handles_mu);
+            loads.emplace_back(blocks[i], g.n());
         }
-    }
     last_load.prepare_s = now_s() - t0;
-    // Batches of ~64 MiB per (k, p, S): the shard-file reads of batch b+1
-    // overlap the reconstruct of batch b (one pipelined multi-GPU call for
-    // the blocks of b that have an erasure).
-    struct Batch {
-        const Group* g;
-        size_t b, e;   // members [b, e)
-    };
-    std::vector<Batch> batches;
-    for (auto& kv : groups) {
-        const Group& g = kv.second;
-        const size_t bb = batch_bytes(true);
-        const size_t per = bb == 0 ? g.members.size() : std::max<size_t>(1, bb / std::max<size_t>(1, size_t(g.k) * g.S));
-        for (size_t b = 0; b < g.members.size(); b += per) batches.push_back({&g, b, std::min(g.members.size(), b + per)});
-    }
-    std::vector<uint8_t> present(tasks.size(), 0), odd(tasks.size(), 0);
-    auto read_batch = [&](const Batch& bt) {
-        const size_t n = size_t(bt.g->k) + bt.g->p;
-        const size_t t0b = first_task[bt.g->members[bt.b]];
-        const size_t nt = (bt.e - bt.b) * n;   // a batch's tasks are contiguous
-        auto read_task = [&](size_t t) {
-            const Task& tk = tasks[t];
-            const VfsOptions& o = blocks[tk.blk].opt_;
-            bool od = false;
-            if (tk.fd >= 0 && blocks[tk.blk].st_->read_shard(tk.shard, tk.fd, *cfg_, o, tk.slot, tk.S, &od) == 0) {
-                present[t] = !(od && o.short_shard_is_erasure);
-                odd[t] = od;
-            }
-        };
-        parallel_for(nt, 32, [&](size_t q) {
-            const size_t t = t0b + q;
-            if (tasks[t].plan == kRead) read_task(t);
-            else if (tasks[t].plan == kPresentUnread) present[t] = 1;
-        });
-        // read_needed_shards: a block whose planned read failed reads the rest too
-        std::vector<size_t> redo;
-        for (size_t q = 0; q < nt; ++q) {
-            const size_t t = t0b + q;
-            if (tasks[t].plan == kRead && (!present[t] || odd[t]))
-                for (size_t s = 0; s < n; ++s) {
-                    const size_t u = first_task[tasks[t].blk] + s;
-                    if (tasks[u].plan == kPresentUnread) {
-                        tasks[u].plan = kRead;
-                        present[u] = 0;
-                        redo.push_back(u);
-                    }
-                }
-        }
-        parallel_for(redo.size(), 32, [&](size_t q) { read_task(redo[q]); });
+    // The shard-file reads of batch b+1 overlap the reconstruct of batch b (one
+    // pipelined multi-GPU call for the blocks of b that have an erasure).
+    const std::vector<Batch> batches = split_batches(groups, batch_bytes(true));
+    auto read_batch = [&](const Batch& bt) {   // every (block, shard) of the batch in one fan-out
+        VirtualBlock::ShardLoad* ld = &loads[bt.first];
+        const size_t n = bt.g->n(), nb = bt.e - bt.b;
+        parallel_for(nb * n, 32, [&](size_t q) { ld[q / n].read(q % n); });
+        std::vector<std::pair<VirtualBlock::ShardLoad*, size_t>> rest;
+        for (size_t j = 0; j < nb; ++j)
+            for (size_t s : ld[j].unread_after_failure()) rest.emplace_back(&ld[j], s);
+        parallel_for(rest.size(), 32, [&](size_t q) { rest[q].first->read(rest[q].second); });
     };
     auto reconstruct_batch = [&](const Batch& bt) {
         const Group& g = *bt.g;
-        const size_t n = size_t(g.k) + g.p;
-        std::vector<size_t> need;
+        std::vector<size_t> need;   // the batch's blocks with an erasure, their slots and presence flags
+        std::vector<uint8_t*> ptrs;
+        std::vector<uint8_t> pres;
         for (size_t j = bt.b; j < bt.e; ++j) {
-            const size_t i = g.members[j];
-            bool missing = false;
-            for (size_t sh = 0; sh < n; ++sh) missing |= !present[first_task[i] + sh] || odd[first_task[i] + sh];
-            if (missing) need.push_back(i);
+            const VirtualBlock::ShardLoad& ld = loads[bt.first + (j - bt.b)];
+            if (!ld.missing()) continue;
+            need.push_back(g.members[j]);
+            ptrs.insert(ptrs.end(), ld.slots.begin(), ld.slots.end());
+            pres.insert(pres.end(), ld.present.begin(), ld.present.end());
         }
         if (!need.empty()) {
-            std::vector<uint8_t*> ptrs(need.size() * n);
-            std::vector<uint8_t> pres(need.size() * n);
-            for (size_t j = 0; j < need.size(); ++j)
-                for (size_t sh = 0; sh < n; ++sh) {
-                    ptrs[j * n + sh] = tasks[first_task[need[j]] + sh].slot;
-                    pres[j * n + sh] = present[first_task[need[j]] + sh];
-                }
             EcStatus es;
             auto r = ReedSolomon::create(g.k, g.p, &es);
             const int rc = r ? shmr_ec_reconstruct_blocks_host(r->handle(), ptrs.data(), pres.data(), need.size(), g.S,
@@ -1631,12 +1624,15 @@ Status VirtualFile::load_blocks(const std::vector<size_t>& block_indices,
                 for (size_t i : need) results[i] = ec_error(rc);
             last_load.blocks += need.size();
         }
+        std::vector<size_t> loaded;
         for (size_t j = bt.b; j < bt.e; ++j) {
             const size_t i = g.members[j];
             if (results[i]) continue;
             blocks[i].st_->buffer.resize(blocks[i].size);   // ec_data[..size]
             blocks[i].st_->buffer_loaded.store(true);
+            loaded.push_back(i);
         }
+        return loaded;
     };
     const double t1 = now_s();
     double io_busy = 0;
@@ -1654,25 +1650,16 @@ Status VirtualFile::load_blocks(const std::vector<size_t>& block_indices,
         reader.get();
         if (bi + 1 < batches.size()) start_read(bi + 1);
         const double tc = now_s();
-        reconstruct_batch(batches[bi]);
+        const std::vector<size_t> loaded = reconstruct_batch(batches[bi]);
         last_load.codec_s += now_s() - tc;
-        if (on_batch) {
-            std::vector<size_t> loaded;
-            for (size_t j = batches[bi].b; j < batches[bi].e; ++j) {
-                const size_t i = batches[bi].g->members[j];
-                if (!results[i]) loaded.push_back(i);
-            }
-            handed.push_back(std::async(std::launch::async, [&on_batch, loaded] { on_batch(loaded); }));
-        }
+        if (on_batch) handed.push_back(std::async(std::launch::async, [&on_batch, loaded] { on_batch(loaded); }));
     }
     last_load.io_s = io_busy;
     last_load.total_s = now_s() - t1;
     for (auto& f : handed) f.get();   // before the blocks' locks are released
-    locks.held.clear();
+    locks.clear();
     parallel_for(others.size(), 16, [&](size_t j) { results[others[j]] = blocks[others[j]].load_block(); });
-    for (auto& r : results)
-        if (r) return r;
-    return std::nullopt;
+    return first_error(results);
 }
 
 Status VirtualFile::drop_buffers() const {

@@ -224,6 +224,7 @@ public:
 private:
     friend class VirtualFile;
     struct State;
+    struct ShardLoad;   // the shard reads of one Erasure block's load
     Status open_handles() const;
     Status load_block() const { return load_block(nullptr, 0); }
     // *reconstructed (if set): an Erasure block needed a reconstruct (on `device`)
@@ -329,6 +330,20 @@ private:
     Status allocate_block();
     size_t batch_bytes(bool load) const;
     std::vector<size_t> blocks_for_range(uint64_t pos, size_t len) const;
+    // The two strategies behind sync_data and load_blocks (`todo`: the listed
+    // blocks that are not buffered), and the steps the batched ones share.
+    struct Group;   // Erasure blocks of one (k, p, S)
+    struct Batch;   // a run of a group's blocks, coded in one call
+    std::vector<Group> erasure_groups(const std::vector<size_t>& indices,
+                                      const std::function<bool(const VirtualBlock&)>& grouped,
+                                      std::vector<size_t>* others) const;
+    static std::vector<Batch> split_batches(const std::vector<Group>& groups, size_t batch_bytes);
+    Status flush_per_block(bool force);
+    Status flush_batched(bool force);
+    using OnBatch = std::function<void(const std::vector<size_t>&)>;
+    Status load_per_block(const std::vector<size_t>& todo, const OnBatch& on_batch, const DuringRebuild& during_rebuild);
+    Status load_batched(const std::vector<size_t>& todo, const OnBatch& on_batch);
+    void open_missing_handles(const std::vector<Group>& groups, std::vector<Status>* results) const;
     std::shared_ptr<const ShmrFsConfig> cfg_;
     VfsOptions opt_;
 };

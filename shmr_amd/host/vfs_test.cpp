@@ -1166,6 +1166,104 @@ void test_read_needed_shards_plan() {
     }
 }
 
+// The file-level load paths on the CPU, by the same method: 5 intact
+// Erasure(1, 4, 2) blocks whose shard files are written directly (S is not a
+// page multiple), loaded as one batch, as three pipelined batches (2 + 2 + 1
+// blocks) and by per-block tasks.  Each path returns the data shards' bytes,
+// reads 4 (needed shards) or 6 files per block, rebuilds nothing, and hands
+// every block to on_batch exactly once, batch by batch.
+void test_virtual_file_load_paths() {
+    auto cfg = test_config();
+    const uint64_t bs = 64 * 1024 - 4096;
+    const size_t nblk = 5, k = 4, p = 2;
+    const size_t S = calculate_shard_size(bs, k);
+    CHECK(S % 4096 != 0);
+    std::vector<VirtualBlock> made(nblk);
+    std::vector<uint8_t> want;
+    for (size_t i = 0; i < nblk; ++i) {
+        CHECK_OK(VirtualBlock::create(21, i + 1, cfg, bs, BlockTopology::erasure(1, k, p), &made[i]));
+        std::vector<uint8_t> block;
+        for (size_t s = 0; s < k + p; ++s) {
+            const auto bytes = random_data(S);   // parity files hold noise: never returned
+            if (s < k) block.insert(block.end(), bytes.begin(), bytes.end());
+            FILE* f = std::fopen(shard_file(*cfg, made[i], s).c_str(), "wb");
+            CHECK(f != nullptr);
+            CHECK(std::fwrite(bytes.data(), 1, S, f) == S);
+            std::fclose(f);
+        }
+        block.resize(bs);
+        want.insert(want.end(), block.begin(), block.end());
+    }
+    // A whole-file read also visits the trailing empty chunk (mod.rs:137-180):
+    // its Single block, as VirtualFile::write leaves one, here already buffered
+    // (copies share the state), so no load path has anything to do for it.
+    VirtualBlock last;
+    CHECK_OK(VirtualBlock::create(21, nblk + 1, cfg, bs, BlockTopology::single(), &last));
+    {
+        uint8_t byte = 0;
+        size_t n = 0;
+        CHECK_OK(last.read(0, &byte, 1, &n));
+        CHECK(last.buffer_loaded());
+    }
+    struct Path {
+        size_t batch_bytes;
+        bool pinned;   // without a device the buffers fall back to pageable memory
+        size_t tasks;
+        std::vector<std::vector<size_t>> handed;   // on_batch's lists, ordered by first block
+    };
+    const Path paths[] = {
+        {0, false, 0, {{0, 1, 2, 3, 4}}},
+        {size_t(2 * bs), false, 0, {{0, 1}, {2, 3}, {4}}},
+        {VirtualFile::kAutoBatch, true, nblk, {{0}, {1}, {2}, {3}, {4}}},
+    };
+    for (bool needed : {true, false})
+        for (const Path& path : paths) {
+            auto view = [&] {   // fresh blocks over the same shard files: nothing buffered, no handle open
+                VirtualFile vf = VirtualFile::new_with(21, nblk * bs);
+                vf.populate(cfg);
+                vf.block_size = bs;
+                vf.pipeline_batch_bytes = path.batch_bytes;
+                for (const VirtualBlock& b : made) {
+                    VirtualBlock v;
+                    v.ino = b.ino;
+                    v.idx = b.idx;
+                    v.size = b.size;
+                    v.topology = b.topology;
+                    v.shards = b.shards;
+                    v.populate(cfg);
+                    vf.blocks.push_back(v);
+                }
+                vf.blocks.push_back(last);
+                VfsOptions o;
+                o.pread_from_start = true;
+                o.read_needed_shards = needed;
+                o.pinned_buffers = path.pinned;
+                vf.set_options(o);
+                return vf;
+            };
+            VirtualFile vf = view();
+            std::vector<uint8_t> rb(want.size(), 0xEE);
+            size_t n = 0;
+            const uint64_t r0 = shard_reads_total();
+            CHECK_OK(vf.read(0, rb.data(), rb.size(), &n));
+            CHECK(n == want.size());
+            CHECK(shard_reads_total() - r0 == (needed ? k : k + p) * nblk);
+            CHECK_SAME(rb, want, bs, S);
+            CHECK(vf.last_load.blocks == 0);
+            CHECK(vf.last_load.tasks == path.tasks);
+            VirtualFile direct = view();
+            std::mutex mu;
+            std::vector<std::vector<size_t>> handed;
+            CHECK_OK(direct.load_blocks({0, 1, 2, 3, 4}, [&](const std::vector<size_t>& loaded) {
+                std::lock_guard<std::mutex> lock(mu);
+                handed.push_back(loaded);
+            }));
+            std::sort(handed.begin(), handed.end());
+            CHECK(handed == path.handed);
+            CHECK(direct.last_load.blocks == 0 && direct.last_load.tasks == path.tasks);
+        }
+}
+
 // Randomised Erasure-block round trips against a byte model: random (k, p) and
 // block sizes, random writes, flush, lose up to p shard files (and sometimes
 // truncate one, an erasure under short_shard_is_erasure), reload, compare;
@@ -1333,6 +1431,7 @@ int main(int argc, char** argv) {
         {"rewrite_erasure_record_reload", test_rewrite_erasure_record_reload},
         {"read_needed_shards", test_read_needed_shards},
         {"read_needed_shards_plan", test_read_needed_shards_plan},
+        {"virtual_file_load_paths", test_virtual_file_load_paths},
         {"virtual_block_erasure_fuzz", test_virtual_block_erasure_fuzz},
         {"virtual_file_erasure_fuzz", test_virtual_file_erasure_fuzz},
     };

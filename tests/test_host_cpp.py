@@ -69,6 +69,7 @@ CPU_CASES = [
     "virtual_file_record_roundtrip",
     "virtual_file_record_fuzz",
     "read_needed_shards_plan",
+    "virtual_file_load_paths",
 ]
 
 
