@@ -273,6 +273,70 @@ int shmr_ec_verify_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_s
                              size_t nblocks, size_t shard_len, uint32_t* d_mismatch,
                              int device, void* stream);
 
+/* ---- scrub: locate and repair one damaged shard per block ------------------ *
+ * A block that fails shmr_ec_verify_batch_dev has every shard present, so no
+ * `present` pattern says what to rebuild.  With parity >= 2 the code itself
+ * says which single shard is wrong.  Per block, with the syndrome
+ * s = C * data ^ stored parity (one byte per parity row and column):
+ *   - parity shard r damaged: only row r differs (the verify word is 1 << r);
+ *   - data shard j damaged: every row differs, and in every column
+ *     s_r == (C[r][j] / C[0][j]) * s_0.
+ * located[b] is SHMR_EC_LOCATE_CLEAN (the verify word is 0), the index in
+ * [0, total) of the one shard whose damage explains the block, or
+ * SHMR_EC_LOCATE_NONE (no single shard does: several are damaged).
+ * What the answer promises:
+ *   - parity >= 3: damage in two shards is never taken for damage in one.
+ *   - parity == 2: the code has distance 3; damage in two shards can look
+ *     like damage in a third, as with any distance-3 code.
+ *   - data shards are told apart by the first group of min(parity, 4) parity
+ *     rows only.  Damage in one data shard plus parity rows beyond that group
+ *     is reported as the data shard; shmr_ec_scrub_batch_dev catches it with
+ *     its closing verify.
+ * Needs 2 <= parity <= 32 (INVALID_ARGUMENT otherwise: below 2 nothing can be
+ * located, above 32 several rows share bit 31 of the verify word). */
+#define SHMR_EC_LOCATE_CLEAN (-1)
+#define SHMR_EC_LOCATE_NONE (-2)
+
+/* Bytes of device scratch shmr_ec_locate_batch_dev needs for nblocks blocks
+ * (positive, never shrinking as nblocks grows); 0 for a codec it refuses. */
+size_t shmr_ec_locate_work_size(const shmr_ec_t* rs, size_t nblocks);
+
+/* Verify and locate nblocks blocks, addressed exactly as
+ * shmr_ec_verify_batch_dev.  d_mismatch (nblocks uint32, device) receives that
+ * call's words unchanged; d_located (nblocks int32, device) the answers above;
+ * d_work is work_bytes >= shmr_ec_locate_work_size(rs, nblocks) bytes of
+ * device scratch (4-byte aligned; too small: INVALID_ARGUMENT, nothing
+ * enqueued).  Read-only over the shards: the verify kernels, then a kernel
+ * that reads one word per tile of a block that is clean or differs in parity
+ * rows only, and the data and first-group parity of the others.  Stream-
+ * ordered, no allocation and no host readback.  NOT capturable: a `stream`
+ * that is being captured into a graph is refused with INVALID_ARGUMENT and
+ * nothing is enqueued (a replayed locate has returned answers that its
+ * eager call does not; until that is understood the call stays out of
+ * graphs, since a scrub writes what locate names). */
+int shmr_ec_locate_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_shard_pitch,
+                             size_t data_block_pitch, const uint8_t* d_parity,
+                             size_t parity_shard_pitch, size_t parity_block_pitch,
+                             size_t nblocks, size_t shard_len, uint32_t* d_mismatch,
+                             int32_t* d_located, void* d_work, size_t work_bytes,
+                             int device, void* stream);
+
+/* The whole scrub, blocking (NOT stream-ordered, NOT capturable: it waits on
+ * `stream` twice and takes pooled device scratch): locate; copy the answers
+ * to the host; rebuild the located shard of each such block in place through
+ * shmr_ec_reconstruct_ptrs_dev's path (present = every shard but that one);
+ * verify again, and demote a rebuilt block that still differs to
+ * SHMR_EC_LOCATE_NONE (its located shard has been rewritten).  Blocks that
+ * locate reports as SHMR_EC_LOCATE_NONE are not written at all.
+ * located_host: nblocks int32 of HOST memory, or NULL.  counts (HOST, 3
+ * entries): blocks clean, repaired, not repairable; written (zeroed first)
+ * only once the arguments and the device have been accepted, so a refused
+ * call leaves them alone. */
+int shmr_ec_scrub_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pitch,
+                            size_t data_block_pitch, uint8_t* d_parity, size_t parity_shard_pitch,
+                            size_t parity_block_pitch, size_t nblocks, size_t shard_len,
+                            int32_t* located_host, uint64_t* counts, int device, void* stream);
+
 /* Reconstruct nblocks blocks in place.  All total shards of block b live at
  * d_shards + b*block_pitch + i*shard_pitch.  present is HOST memory,
  * nblocks x total flags (row-major).  Blocks may have different presence

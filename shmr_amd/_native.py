@@ -57,6 +57,13 @@ SIGNATURES = [
     ("shmr_ec_verify_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _sz, _sz, ctypes.c_void_p,
       ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_locate_work_size", _sz, [ctypes.c_void_p, _sz]),
+    ("shmr_ec_locate_batch_dev", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _sz, _sz, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_scrub_batch_dev", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _sz, _sz,
+      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_void_p]),
     ("shmr_ec_reconstruct_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_int, ctypes.c_int,
       ctypes.c_void_p]),

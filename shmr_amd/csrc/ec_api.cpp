@@ -867,6 +867,104 @@ int shmr_ec_verify_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_s
     });
 }
 
+// ---- scrub: locate and repair one damaged shard per block ----------------------------
+size_t shmr_ec_locate_work_size(const shmr_ec_t* rs, size_t nblocks) {
+    return rs && rs->codec->locate_plan() ? core::locate_work_bytes(*rs->codec, nblocks) : 0;
+}
+
+int shmr_ec_locate_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_shard_pitch, size_t data_block_pitch,
+                             const uint8_t* d_parity, size_t parity_shard_pitch, size_t parity_block_pitch,
+                             size_t nblocks, size_t shard_len, uint32_t* d_mismatch, int32_t* d_located, void* d_work,
+                             size_t work_bytes, int device, void* stream) {
+    return guarded([&]() -> int {
+        if (!rs || !rs->codec->locate_plan()) return SHMR_EC_INVALID_ARGUMENT;
+        Codec& c = *rs->codec;
+        const bool given = d_data && d_parity && d_mismatch && d_located && d_work &&
+                           (uintptr_t(d_mismatch) | uintptr_t(d_located) | uintptr_t(d_work)) % alignof(uint32_t) == 0 &&
+                           work_bytes >= core::locate_work_bytes(c, nblocks);
+        return batch_dev(nblocks, shard_len, device, [&] { return arg_ok(given); }, [&] {
+            const core::Layout L{d_data, const_cast<uint8_t*>(d_parity), data_block_pitch, data_shard_pitch,
+                                 parity_block_pitch, parity_shard_pitch, c.k()};
+            return core::locate_on_device(c, device, L, nblocks, shard_len, d_mismatch, d_located,
+                                          static_cast<uint32_t*>(d_work), static_cast<hipStream_t>(stream));
+        });
+    });
+}
+
+int shmr_ec_scrub_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pitch, size_t data_block_pitch,
+                            uint8_t* d_parity, size_t parity_shard_pitch, size_t parity_block_pitch, size_t nblocks,
+                            size_t shard_len, int32_t* located_host, uint64_t* counts, int device, void* stream_) {
+    return guarded([&]() -> int {
+        if (!rs || !counts || !rs->codec->locate_plan()) return SHMR_EC_INVALID_ARGUMENT;
+        // (counts are written only by a call that is accepted: an empty batch, or below)
+        if (nblocks == 0) counts[0] = counts[1] = counts[2] = 0;
+        Codec& c = *rs->codec;
+        hipStream_t stream = static_cast<hipStream_t>(stream_);
+        return batch_dev(nblocks, shard_len, device, [&] { return arg_ok(d_data && d_parity); }, [&]() -> int {
+            bool capturing = false;
+            int rc = core::device_init(device, stream);
+            if (rc || (rc = core::capture_state(stream, &capturing))) return rc;
+            if (capturing) return SHMR_EC_INVALID_ARGUMENT;   // it waits for its own results
+            counts[0] = counts[1] = counts[2] = 0;
+            const unsigned k = c.k(), t = k + c.p();
+            const core::Layout L{d_data, d_parity, data_block_pitch, data_shard_pitch, parity_block_pitch,
+                                 parity_shard_pitch, k};
+            // pooled scratch (grown without a free): the words, the answers, the candidate bitmaps
+            const size_t words_bytes = size_t(core::round_up(nblocks * sizeof(uint32_t), 256));
+            core::StagingLease lease;
+            lease.s = core::StagingPool::get().acquire(device, 2 * words_bytes + core::locate_work_bytes(c, nblocks), &rc);
+            if (!lease.s) return rc;
+            uint32_t* d_words = reinterpret_cast<uint32_t*>(lease.s->dbuf);
+            int32_t* d_located = reinterpret_cast<int32_t*>(lease.s->dbuf + words_bytes);
+            uint32_t* d_cand = reinterpret_cast<uint32_t*>(lease.s->dbuf + 2 * words_bytes);
+            // (a failure below still waits: the scratch goes back to the pool idle)
+            auto fetch = [&](void* dst, const void* src) -> int {
+                const hipError_t e = hipMemcpyAsync(dst, src, nblocks * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+                const hipError_t w = core::sync_stream(stream);
+                return e == hipSuccess && w == hipSuccess ? SHMR_EC_OK : SHMR_EC_DEVICE_ERROR;
+            };
+            std::vector<int32_t> own;
+            int32_t* located = located_host;
+            if (!located) {
+                own.resize(nblocks);
+                located = own.data();
+            }
+            rc = core::locate_on_device(c, device, L, nblocks, shard_len, d_words, d_located, d_cand, stream);
+            const int frc = fetch(located, d_located);
+            if (rc || frc) return rc ? rc : frc;
+            // the located shard of every such block, rebuilt from the block's other shards
+            std::vector<size_t> hit;
+            for (size_t b = 0; b < nblocks; ++b) {
+                if (located[b] >= 0) hit.push_back(b);
+                else ++counts[located[b] == SHMR_EC_LOCATE_CLEAN ? 0 : 2];
+            }
+            if (hit.empty()) return SHMR_EC_OK;
+            std::vector<uint64_t> tab(hit.size() * t);
+            std::vector<uint8_t> present(hit.size() * t, 1);
+            for (size_t i = 0; i < hit.size(); ++i) {
+                const size_t b = hit[i];
+                for (unsigned s = 0; s < t; ++s)
+                    tab[i * t + s] = s < k ? uint64_t(uintptr_t(d_data + b * data_block_pitch + s * data_shard_pitch))
+                                           : uint64_t(uintptr_t(d_parity + b * parity_block_pitch +
+                                                                (s - k) * parity_shard_pitch));
+                present[i * t + size_t(located[b])] = 0;
+            }
+            rc = core::ptrs_launch(c, tab.data(), present.data(), hit.size(), shard_len, false, device, stream,
+                                   core::kDecode, false, false);
+            // the closing verify: damage beyond what locate looked at shows here
+            if (rc == SHMR_EC_OK) rc = core::verify_on_device(c, device, L, nblocks, shard_len, d_words, stream);
+            std::vector<uint32_t> words(nblocks);
+            const int wrc = fetch(words.data(), d_words);
+            if (rc || wrc) return rc ? rc : wrc;
+            for (size_t b : hit) {
+                if (words[b] != 0) located[b] = SHMR_EC_LOCATE_NONE;
+                ++counts[words[b] != 0 ? 2 : 1];
+            }
+            return SHMR_EC_OK;
+        });
+    });
+}
+
 int shmr_ec_reconstruct_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard_pitch, size_t block_pitch,
                                   const uint8_t* present, size_t nblocks, size_t shard_len, int data_only, int device,
                                   void* stream) {

@@ -9,6 +9,7 @@
 #include <unordered_set>
 
 #include "knobs.hpp"
+#include "locate_plan.hpp"
 #include "run_split.hpp"
 
 namespace shmr {
@@ -1114,6 +1115,54 @@ int verify_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
         });
         if (rc) return rc;
     }
+    return SHMR_EC_OK;
+}
+
+// ===========================================================================
+// Single-shard location (the second half of a scrub).  The parity check above
+// into d_mismatch; the candidate bitmaps preset to all ones; the locate kernel
+// over the first row group only, split as a verify's launches (4 KiB tiles);
+// the resolve kernel.  One more launch group is counted.
+// ===========================================================================
+size_t locate_work_bytes(const Codec& c, uint64_t nblocks) {
+    return size_t(round_up(std::max<uint64_t>(nblocks, 1) * locate::bitmap_words(c.k()) * sizeof(uint32_t), 256));
+}
+
+int locate_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint64_t len, uint32_t* d_mismatch,
+                     int32_t* d_located, uint32_t* d_cand, hipStream_t stream) {
+    const std::shared_ptr<Plan> lplan = c.locate_plan();
+    if (!lplan) return SHMR_EC_INVALID_ARGUMENT;
+    // Not inside a graph capture (shmr_ec.h): refused before anything is enqueued.
+    int rc = device_init(dev, stream);
+    if (rc) return rc;
+    bool capturing = false;
+    if ((rc = capture_state(stream, &capturing))) return rc;
+    if (capturing) return SHMR_EC_INVALID_ARGUMENT;
+    rc = verify_on_device(c, dev, L, nblocks, len, d_mismatch, stream);
+    if (rc || nblocks == 0) return rc;
+    Plan& plan = *c.encode_plan();
+    const unsigned rows = locate::rows_used(plan.m);
+    SHMR_HIP_TRY(kern::launch_locate_preset(d_cand, nblocks, plan.k, stream));
+    const uint8_t *dplan = nullptr, *dratio = nullptr;
+    rc = plan_on_device(plan, dev, stream, false, &dplan);
+    if (rc) return rc;
+    rc = plan_on_device(*lplan, dev, stream, false, &dratio);
+    if (rc) return rc;
+    const bool aligned = layout_aligned16(L) || unaligned_vector(dev);
+    kern::ApplyArgs a = apply_args(L, plan, dplan, len);
+    a.blk_first = 0;
+    a.blk_stride = 1;
+    a.nblk = nblocks;
+    a.in_identity = 1;
+    a.row0 = 0;
+    count_device(dev, kDevLaunches);
+    rc = launch_split(a, len, kern::tile_bytes(1), aligned ? 0 : -1, aligned ? 1 : 2, [&](int mode) -> int {
+        SHMR_HIP_TRY(kern::launch_locate(a, dratio + plan_tab_off(lplan->k, lplan->m), d_mismatch, d_cand, rows, plan.m,
+                                         mode, stream));
+        return SHMR_EC_OK;
+    });
+    if (rc) return rc;
+    SHMR_HIP_TRY(kern::launch_locate_resolve(d_mismatch, d_cand, d_located, nblocks, plan.k, plan.m, stream));
     return SHMR_EC_OK;
 }
 

@@ -271,6 +271,19 @@ int verify_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
 // kern::verify_chunks (the tools build: the knob "encode.chunks" = 1 / 2 where
 // set, its measurement).
 int verify_chunks(unsigned rows);
+// Single-shard location of nblocks blocks laid out per `L` as for
+// verify_on_device, for codecs with a locate plan (2 <= p <= 32, else
+// INVALID_ARGUMENT with nothing enqueued): verify_on_device into d_mismatch,
+// then d_located[b] = -1 (a codeword), the index of the one shard whose damage
+// explains block b's syndromes, or -2 (locate_plan.hpp resolve).  Data shards
+// are told apart by the first row group (min(p, 4) parity rows) only.
+// d_cand: locate_work_bytes(c, nblocks) bytes of device scratch, 4-byte
+// aligned.  Stream-ordered as verify_on_device, but a stream that is being
+// captured is refused (INVALID_ARGUMENT, nothing enqueued: shmr_ec.h); nothing
+// but the three result arrays is written.
+size_t locate_work_bytes(const Codec& c, uint64_t nblocks);
+int locate_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint64_t len, uint32_t* d_mismatch,
+                     int32_t* d_located, uint32_t* d_cand, hipStream_t stream);
 // The blocks slots[0 .. n) (ascending, distinct) of a single-plan launch set.
 int launch_slots(Plan& plan, int dev, const Layout& L, const uint64_t* slots, uint64_t n, uint64_t len,
                  hipStream_t stream, OpClass op);

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "locate_plan.hpp"
 
 namespace shmr {
 namespace gf {
@@ -145,6 +146,16 @@ Codec::Codec(unsigned k, unsigned p) : k_(k), p_(p), matrix_(build_matrix(k, k +
     for (unsigned i = 0; i < k; ++i) plan->in_idx.push_back(uint16_t(i));
     for (unsigned r = 0; r < p; ++r) plan->out_idx.push_back(uint16_t(k + r));
     encode_plan_ = plan;
+    if (p < locate::kMinParity || p > locate::kMaxParity) return;
+    const unsigned R = locate::rows_used(p);
+    auto lp = std::make_shared<Plan>();
+    lp->k = k;
+    lp->m = R - 1;
+    lp->rows = Matrix(R - 1, k);
+    if (!locate::ratio_rows(matrix_.row(k), k, R, div, lp->rows.d.data())) return;
+    lp->in_idx = plan->in_idx;
+    for (unsigned r = 1; r < R; ++r) lp->out_idx.push_back(uint16_t(k + r));   // (unused: nothing is stored)
+    locate_plan_ = lp;
 }
 
 // Device plan images live in the per-device arenas of ec_core (process

@@ -94,6 +94,10 @@ public:
     unsigned p() const { return p_; }
     const Matrix& matrix() const { return matrix_; }
     std::shared_ptr<Plan> encode_plan() const { return encode_plan_; }
+    // The ratio rows of single-shard location (locate_plan.hpp ratio_rows) in
+    // the shape of an encode plan: k inputs, min(p, 4) - 1 rows, row r-1 entry j
+    // = C[r][j] / C[0][j].  Null when the codec cannot locate (p < 2 or p > 32).
+    std::shared_ptr<Plan> locate_plan() const { return locate_plan_; }
 
     // Crate get_data_decode_matrix: inverse of the rows of `valid`,
     // LRU-cached (capacity 254) keyed by `invalid`.
@@ -114,6 +118,7 @@ private:
     unsigned k_, p_;
     Matrix matrix_;
     std::shared_ptr<Plan> encode_plan_;
+    std::shared_ptr<Plan> locate_plan_;
 
     std::mutex mu_;
     // LRU of decode matrices (crate semantics), key = invalid indices.

@@ -295,6 +295,24 @@ size_t kernel_inventory(KernelInfo* out, size_t cap);
 constexpr int verify_chunks(unsigned rows) { return rows >= 3 ? 2 : 1; }
 hipError_t launch_verify(const ApplyArgs& a, uint32_t* mismatch, unsigned rows, int u, int mode, hipStream_t stream);
 
+// The single-shard location kernels (gf_locate.hip; shmr_ec_locate_batch_dev),
+// behind a launch_verify of the same blocks: `a` as for launch_verify of the
+// first row group (a.row0 = 0, rows = min(p, 4) in [2, 4]); mismatch[j] the
+// complete verify word of launch block j (p <= 32 parity rows: a bit each);
+// qtab the tables of the codec's locate plan (PermTab[k][rows - 1]).  In a
+// block whose every parity row differs, clears bit t of cand[j * words ..]
+// (words = ceil(k / 32), preset to all ones by the caller) for every data
+// shard t that this launch's tiles rule out; reads one word per tile of any
+// other block.  Modes as launch_verify, 4 KiB tiles; a bounded grid strides
+// over the tiles.  Not part of kernel_inventory.
+hipError_t launch_locate(const ApplyArgs& a, const uint8_t* qtab, const uint32_t* mismatch, uint32_t* cand,
+                         unsigned rows, unsigned p, int mode, hipStream_t stream);
+// cand[0 .. nblk * words) = all ones (a kernel: see gf_locate.hip).
+hipError_t launch_locate_preset(uint32_t* cand, uint64_t nblk, unsigned k, hipStream_t stream);
+// located[b] = locate::resolve(mismatch[b], cand + b * words, k, p) (locate_plan.hpp), b < nblk.
+hipError_t launch_locate_resolve(const uint32_t* mismatch, const uint32_t* cand, int32_t* located, uint64_t nblk,
+                                 unsigned k, unsigned p, hipStream_t stream);
+
 // The submission queue's completion mark (submit.cpp): a one-wave kernel on
 // `stream` that stores `seq` to `word` -- pinned host memory, a system-scope
 // release store -- once every earlier kernel of the stream has completed, so

@@ -1,0 +1,244 @@
+// GF(2^8) single-shard location kernels for gfx950 (MI355X / CDNA4): the second
+// half of a scrub (shmr_ec_locate_batch_dev), behind the parity check of
+// gf_verify.hip.
+//
+//   cand[j] bit t stays set  <=>  in every column of block j,
+//   s_r == q[r][t] (x) s_0 for r = 1 .. R-1,   s = C (x) data ^ stored parity
+//
+// (locate_plan.hpp: what a damaged data shard t, and only it, leaves behind.)
+// A read-only pass over the data and the stored parity of the first row group,
+// R = min(p, 4) rows; the only stores are vector global atomics (AND) to the
+// candidate bitmap, which the caller presets to all ones on the same stream.
+//
+//  * The tile loop is the parity check's (same ApplyArgs, plan staging, ring,
+//    loads and modes), grid-strided over a bounded grid.  A tile first reads
+//    its block's verify word -- a scalar load, the branch is workgroup-uniform
+//    -- and goes on to the next tile unless every parity row differs: clean
+//    blocks and blocks with one damaged parity shard cost one word per tile,
+//    and a workgroup that meets no damaged block never stages a plan.
+//  * Damaged tiles: the R syndrome chunks as the parity check forms them (one
+//    16-byte chunk per lane: rate on damaged blocks is no goal), then per data
+//    shard t one more mac of s_0 with the ratio tables and a compare.  A
+//    column with a zero syndrome eliminates nobody, so nothing is masked.
+//    One ballot per shard; one lane per wave ANDs the wave's survivors into
+//    the block's bitmap, 32 shards at a time, where any were eliminated.
+//  * MODE 0 full tiles, MODE 1 one bounds-checked partial tile per block,
+//    MODE 2 byte-granular at any alignment: bytes at or past len are read by
+//    neither side (both are zero there, as in the parity check).
+//  * The resolve kernel: one thread per block, locate::resolve.
+//
+// Like the parity check kernels these are not gf_apply_kernel instantiations
+// and not part of shmr_ec_kernel_inventory.
+#include <hip/hip_runtime.h>
+
+#include "gf_tile.hpp"
+#include "locate_plan.hpp"
+
+namespace shmr {
+namespace kern {
+
+namespace {
+
+// The lane's syndrome chunk of every row: s[r] = XOR_t C[r][t] (x) data[t] ^ stored[r].
+template <int R, int MODE>
+__device__ __forceinline__ void syndrome_tile(const ApplyArgs& a, const Ctx& c, const uint8_t* ib, const uint8_t* ob,
+                                              uint64_t col, uint32_t (&s)[R][4]) {
+    const uint64_t len = a.len;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[r][j] = 0u;
+    auto load = [&](u32x4& buf, uint32_t t) { buf = ld<MODE, 0>(ib + c.s_in_off[t], col, len); };
+    auto consume = [&](const u32x4& buf, uint32_t t) {
+        Tab tb[R];
+        read_tabs<R>(c, t, tb);
+        mac<R, 0>(s, buf, tb);
+    };
+    u32x4 ring[2];
+    load(ring[0], 0);
+    __builtin_amdgcn_sched_barrier(0);
+    ring2_peeled(load, consume, a.k, ring);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const u32x4 par = ld<MODE, 0>(ob + c.s_out_off[r], col, len);
+        s[r][0] ^= par.x;
+        s[r][1] ^= par.y;
+        s[r][2] ^= par.z;
+        s[r][3] ^= par.w;
+    }
+}
+
+// The parity check launch of row group 0 (rows = R) plus what location adds.
+struct LocateArgs {
+    ApplyArgs a;
+    const uint8_t* qtab;        // the locate plan's tables, PermTab[k][R - 1] (gf256.hpp Codec::locate_plan)
+    const uint32_t* mismatch;   // [nblk] verify words, complete before this launch
+    uint32_t* cand;             // [nblk][words] candidate bitmaps, preset to all ones
+    uint32_t all_rows;          // the verify word of a block whose every parity row differs
+    uint32_t words;             // locate::bitmap_words(k)
+};
+
+// LDS: the staged encode plan of R rows (gf_tile.hpp stage_plan), then the ratio tables.
+__host__ __device__ inline uint32_t ratio_tab_off(uint32_t k, uint32_t R) { return (k * R * 32 + k * 8 + R * 8 + 15) & ~15u; }
+
+template <int R, int MODE>
+__global__ __launch_bounds__(kThreads) void gf_locate_kernel(const LocateArgs la) {
+    constexpr int TH = kThreads;
+    constexpr int Q = R - 1;
+    const ApplyArgs& a = la.a;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t k = a.k;
+    Ctx c{}, qc{};
+    bool staged = false;
+    const uint64_t tb = uint64_t(TH) * 16;
+    const uint32_t tpb = a.tiles_per_block;
+    for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+        const uint64_t j = tile / tpb, cc = tile - j * tpb;
+        if (as_const<cu32>(la.mismatch)[j] != la.all_rows) continue;   // clean, or parity rows only
+        if (!staged) {   // (workgroup-uniform: every lane of the workgroup is here)
+            stage_plan<R, TH, false>(a, a.plan, smem, c, 0);
+            u32x4* s_q = reinterpret_cast<u32x4*>(smem + ratio_tab_off(k, R));
+            const u32x4* gq = reinterpret_cast<const u32x4*>(la.qtab);
+            for (uint32_t i = threadIdx.x; i < k * Q * 2; i += TH) s_q[i] = gq[i];
+            qc.s_tab = s_q;
+            __syncthreads();
+            staged = true;
+        }
+        const uint64_t blk = a.blk_first + j * a.blk_stride;
+        const uint8_t* ib = a.in_base + blk * a.in_bpitch;
+        const uint8_t* ob = a.out_base + blk * a.out_bpitch;
+        uint32_t s[R][4];
+        syndrome_tile<R, MODE>(a, c, ib, ob, a.col_base + cc * tb + uint64_t(threadIdx.x) * 16, s);
+        uint32_t any = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) any |= s[r][0] | s[r][1] | s[r][2] | s[r][3];
+        // every lane of the wave is here (no lane leaves a tile early); no barrier follows
+        if (__builtin_amdgcn_ballot_w64(any != 0) == 0) continue;   // this wave's columns eliminate nobody
+        const u32x4 s0{s[0][0], s[0][1], s[0][2], s[0][3]};
+        uint32_t* bw = la.cand + j * la.words;
+        uint32_t keep = 0xffffffffu;   // wave-uniform: the survivors among shards [t & ~31, t]
+        for (uint32_t t = 0; t < k; ++t) {
+            Tab tq[Q];
+            read_tabs<Q>(qc, t, tq);
+            uint32_t m[Q][4];
+#pragma unroll
+            for (int r = 0; r < Q; ++r)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) m[r][i] = 0u;
+            mac<Q, 0>(m, s0, tq);
+            uint32_t d = 0;
+#pragma unroll
+            for (int r = 0; r < Q; ++r)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) d |= s[r + 1][i] ^ m[r][i];
+            if (__builtin_amdgcn_ballot_w64(d != 0) != 0) keep &= ~(1u << (t & 31u));
+            if ((t & 31u) == 31u || t + 1 == k) {
+                if (keep != 0xffffffffu && (threadIdx.x & 63u) == 0) atomicAnd(bw + (t >> 5), keep);
+                keep = 0xffffffffu;
+            }
+        }
+    }
+}
+
+// Every data shard of every block is a candidate until a tile rules it out.
+// (A kernel: a hipMemsetAsync of 0xff did the same eagerly, but as a memset
+// node of a captured graph it left other bytes behind on replay)
+__global__ __launch_bounds__(kThreads) void gf_locate_preset_kernel(uint32_t* cand, uint64_t nwords) {
+    for (uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x; i < nwords; i += uint64_t(gridDim.x) * kThreads)
+        cand[i] = 0xffffffffu;
+}
+
+__global__ __launch_bounds__(kThreads) void gf_locate_resolve_kernel(const uint32_t* mismatch, const uint32_t* cand,
+                                                                     int32_t* located, uint64_t nblk, uint32_t k,
+                                                                     uint32_t p) {
+    const uint64_t b = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+    if (b >= nblk) return;
+    located[b] = locate::resolve(mismatch[b], cand + b * locate::bitmap_words(k), k, p);
+}
+
+// Workgroups of a locate launch: the tile loop strides over them.  A clean
+// batch runs them all for one word per tile each, so the grid is bounded --
+// the 256-lane workgroups a CU holds at once (2048 lanes), for every CU of the
+// current device -- instead of one workgroup per tile.
+constexpr uint64_t kLocateWgsPerCu = 8;
+hipError_t locate_grid(uint64_t* grid) {
+    int dev = 0, cus = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+    *grid = uint64_t(cus < 1 ? 1 : cus) * kLocateWgsPerCu;
+    return hipSuccess;
+}
+
+template <int R, int MODE>
+hipError_t launch_locate_one(const LocateArgs& la, hipStream_t stream) {
+    const ApplyArgs& a = la.a;
+    const size_t lds = size_t(ratio_tab_off(a.k, R)) + size_t(a.k) * (R - 1) * 32;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gf_locate_kernel<R, MODE>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+        if (e != hipSuccess) return e;
+    }
+    uint64_t grid = 0;
+    const hipError_t ge = locate_grid(&grid);
+    if (ge != hipSuccess) return ge;
+    if (grid > a.ntiles) grid = a.ntiles;
+    if (grid == 0) return hipSuccess;
+    // (by name, never through a function-pointer variable: gf_tile.hpp launch_one)
+    hipLaunchKernelGGL((gf_locate_kernel<R, MODE>), dim3(uint32_t(grid)), dim3(kThreads), lds, stream, la);
+    return hipGetLastError();
+}
+
+template <int R>
+hipError_t dispatch_locate(const LocateArgs& la, int mode, hipStream_t stream) {
+    switch (mode) {
+        case 0: return launch_locate_one<R, 0>(la, stream);
+        case 1: return launch_locate_one<R, 1>(la, stream);
+        case 2: return launch_locate_one<R, 2>(la, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_locate(const ApplyArgs& a, const uint8_t* qtab, const uint32_t* mismatch, uint32_t* cand,
+                         unsigned rows, unsigned p, int mode, hipStream_t stream) {
+    LocateArgs la;
+    la.a = a;
+    la.qtab = qtab;
+    la.mismatch = mismatch;
+    la.cand = cand;
+    la.all_rows = locate::all_rows(p);
+    la.words = locate::bitmap_words(a.k);
+    switch (rows) {
+        case 2: return dispatch_locate<2>(la, mode, stream);
+        case 3: return dispatch_locate<3>(la, mode, stream);
+        case 4: return dispatch_locate<4>(la, mode, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_locate_preset(uint32_t* cand, uint64_t nblk, unsigned k, hipStream_t stream) {
+    const uint64_t nwords = nblk * locate::bitmap_words(k);
+    uint64_t grid = (nwords + kThreads - 1) / kThreads, cap = 0;
+    if (grid == 0) return hipSuccess;
+    const hipError_t ge = locate_grid(&cap);
+    if (ge != hipSuccess) return ge;
+    if (grid > cap) grid = cap;
+    hipLaunchKernelGGL(gf_locate_preset_kernel, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, cand, nwords);
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_resolve(const uint32_t* mismatch, const uint32_t* cand, int32_t* located, uint64_t nblk,
+                                 unsigned k, unsigned p, hipStream_t stream) {
+    const uint64_t grid = (nblk + kThreads - 1) / kThreads;
+    if (grid == 0) return hipSuccess;
+    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gf_locate_resolve_kernel, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, mismatch, cand,
+                       located, nblk, uint32_t(k), uint32_t(p));
+    return hipGetLastError();
+}
+
+}  // namespace kern
+}  // namespace shmr

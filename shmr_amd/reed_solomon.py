@@ -218,19 +218,8 @@ class ReedSolomon:
         e.g. the static result buffer of a captured graph.  Enqueued on torch's
         current stream; nothing else is written."""
         import torch
-        B = data.shape[0]
-        dbp = data.stride(0)
-        pbp = parity.stride(0)
-        dsp = data_shard_pitch if data_shard_pitch is not None else (data.stride(1) if data.dim() == 3 else dbp // self.data_shard_count())
-        psp = parity_shard_pitch if parity_shard_pitch is not None else (parity.stride(1) if parity.dim() == 3 else pbp // self.parity_shard_count())
-        L = shard_len if shard_len is not None else dsp
-        if parity.shape[0] != B:
-            raise ValueError(f"data has {B} blocks, parity {parity.shape[0]}")
-        self._check_batch_tensor(data, self.data_shard_count(), dsp, L)
-        self._check_batch_tensor(parity, self.parity_shard_count(), psp, L)
-        self._check_addressable(data, parity)
-        if not data.is_cuda:
-            raise TypeError("verify_batch_dev takes tensors on the GPU")
+        B, dsp, dbp, psp, pbp, L = self._device_regions(data, parity, shard_len, "verify_batch_dev",
+                                                        data_shard_pitch, parity_shard_pitch)
         if out is None:
             out = torch.empty(B, dtype=torch.int32, device=data.device)
         elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.device != data.device
@@ -247,12 +236,95 @@ class ReedSolomon:
         """``verify_batch_dev`` of one ``[B, k + p, pitch]`` tensor holding every
         shard of a block side by side (the layout ``reconstruct_batch_dev``
         takes), split into its data and parity regions."""
+        data, parity = self._split_shards(shards)
+        return self.verify_batch_dev(data, parity, shard_len=shard_len, device=device, out=out)
+
+    def _device_regions(self, data, parity, shard_len, what, data_shard_pitch=None, parity_shard_pitch=None):
+        """The pitches and tensor checks of the calls that read a data and a
+        stored-parity region on the GPU (verify, locate, scrub), in
+        ``encode_batch_dev``'s order -> (B, dsp, dbp, psp, pbp, L)."""
+        B = data.shape[0]
+        dbp, pbp = data.stride(0), parity.stride(0)
+        dsp = data_shard_pitch if data_shard_pitch is not None else (data.stride(1) if data.dim() == 3 else dbp // self.data_shard_count())
+        psp = parity_shard_pitch if parity_shard_pitch is not None else (parity.stride(1) if parity.dim() == 3 else pbp // self.parity_shard_count())
+        L = shard_len if shard_len is not None else dsp
+        if parity.shape[0] != B:
+            raise ValueError(f"data has {B} blocks, parity {parity.shape[0]}")
+        self._check_batch_tensor(data, self.data_shard_count(), dsp, L)
+        self._check_batch_tensor(parity, self.parity_shard_count(), psp, L)
+        self._check_addressable(data, parity)
+        if not data.is_cuda:
+            raise TypeError(f"{what} takes tensors on the GPU")
+        return B, dsp, dbp, psp, pbp, L
+
+    def locate_work_size(self, nblocks: int) -> int:
+        """Bytes of device scratch ``shmr_ec_locate_batch_dev`` needs for nblocks blocks."""
+        return int(self._L.shmr_ec_locate_work_size(self._h, nblocks))
+
+    def locate_batch_dev(self, data, parity, shard_len: Optional[int] = None, device: Optional[int] = None):
+        """Verify and locate (``shmr_ec_locate_batch_dev``): data and parity as
+        ``verify_batch_dev`` takes them; nothing but the results is written.
+
+        Returns ``(mismatch, located)``, two ``torch.int32`` tensors ``[B]`` on
+        the tensors' device: the words of ``verify_batch_dev``, and per block
+        -1 (``LOCATE_CLEAN``: a codeword), the index in [0, k + p) of the one
+        shard whose damage explains the block, or -2 (``LOCATE_NONE``: no single
+        shard does).  Needs 2 <= p <= 32 (``InvalidArgument`` otherwise).  With
+        p = 2 damage in two shards can pass for damage in a third; data shards
+        are told apart by the first min(p, 4) parity rows only (shmr_ec.h).
+        Enqueued on torch's current stream.  Not for graph capture: the results
+        and the scratch are allocated with ``torch.empty`` on every call, and
+        the native call refuses a stream that is being captured (shmr_ec.h)."""
+        import torch
+        B, dsp, dbp, psp, pbp, L = self._device_regions(data, parity, shard_len, "locate_batch_dev")
+        mismatch = torch.empty(B, dtype=torch.int32, device=data.device)
+        located = torch.empty(B, dtype=torch.int32, device=data.device)
+        work = torch.empty(self.locate_work_size(B), dtype=torch.uint8, device=data.device)
+        dev, stream = self._stream_and_device(data)
+        dev = dev if device is None else int(device)
+        _check(self._L.shmr_ec_locate_batch_dev(self._h, ctypes.c_void_p(data.data_ptr()), dsp, dbp,
+                                                ctypes.c_void_p(parity.data_ptr()), psp, pbp, B, L,
+                                                ctypes.c_void_p(mismatch.data_ptr()), ctypes.c_void_p(located.data_ptr()),
+                                                ctypes.c_void_p(work.data_ptr()), work.numel(), dev, stream))
+        return mismatch, located
+
+    def _split_shards(self, shards):
         if shards.dim() != 3:
             raise TypeError("shards must be a [blocks, total, bytes] tensor")
         k, t = self.data_shard_count(), self.total_shard_count()
         if shards.shape[1] != t:
             raise Error(-1 if shards.shape[1] < t else -2)       # TooFewShards / TooManyShards
-        return self.verify_batch_dev(shards[:, :k], shards[:, k:], shard_len=shard_len, device=device, out=out)
+        return shards[:, :k], shards[:, k:]
+
+    def locate_shards_dev(self, shards, shard_len: Optional[int] = None, device: Optional[int] = None):
+        """``locate_batch_dev`` of one ``[B, k + p, pitch]`` tensor, as ``verify_shards_dev``."""
+        data, parity = self._split_shards(shards)
+        return self.locate_batch_dev(data, parity, shard_len=shard_len, device=device)
+
+    def scrub_batch_dev(self, data, parity, shard_len: Optional[int] = None, device: Optional[int] = None):
+        """The whole scrub (``shmr_ec_scrub_batch_dev``), blocking: locate, rebuild
+        the located shard of each such block in place through the reconstruct
+        kernels, verify again.  Blocks that are not locatable are not written.
+
+        Returns ``(located, counts)``: a numpy int32 ``[B]`` as ``locate_batch_dev``
+        gives it, a rebuilt block that still differs demoted to -2, and the
+        tuple (clean, repaired, not repairable).  Waits on torch's current
+        stream; not capturable."""
+        B, dsp, dbp, psp, pbp, L = self._device_regions(data, parity, shard_len, "scrub_batch_dev")
+        located = np.zeros(B, dtype=np.int32)
+        counts = (ctypes.c_uint64 * 3)()
+        dev, stream = self._stream_and_device(data)
+        dev = dev if device is None else int(device)
+        _check(self._L.shmr_ec_scrub_batch_dev(self._h, ctypes.c_void_p(data.data_ptr()), dsp, dbp,
+                                               ctypes.c_void_p(parity.data_ptr()), psp, pbp, B, L,
+                                               located.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), counts,
+                                               dev, stream))
+        return located, tuple(int(x) for x in counts)
+
+    def scrub_shards_dev(self, shards, shard_len: Optional[int] = None, device: Optional[int] = None):
+        """``scrub_batch_dev`` of one ``[B, k + p, pitch]`` tensor, as ``verify_shards_dev``."""
+        data, parity = self._split_shards(shards)
+        return self.scrub_batch_dev(data, parity, shard_len=shard_len, device=device)
 
     # -- device-resident batches (torch tensors on the GPU) ------------------------
     @staticmethod
