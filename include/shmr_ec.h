@@ -337,6 +337,60 @@ int shmr_ec_scrub_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pi
                             size_t parity_block_pitch, size_t nblocks, size_t shard_len,
                             int32_t* located_host, uint64_t* counts, int device, void* stream);
 
+/* ---- parity delta update: writes into device-resident blocks ---------------- *
+ * Changes part of a resident block and keeps its parity valid without
+ * re-encoding it.  The code is linear: for every update,
+ *   - bytes [offset, offset + len) of data shard `shard` of block `block`
+ *     become d_src[src_offset .. src_offset + len);
+ *   - every parity row r gets parity_r[col] ^= C[r][shard] * (old[col] ^ new[col])
+ *     on those columns.
+ * No other byte is written: not the other shards, the pitch padding past
+ * shard_len, or the other blocks.  The syndrome of every block is unchanged:
+ * a codeword stays a codeword, a damaged block keeps exactly its damage.
+ * Traffic is (3 + 2 * parity) * len per update instead of a whole encode. */
+typedef struct shmr_ec_update {
+    uint32_t block;      /* block index, addressed as in shmr_ec_encode_batch_dev */
+    uint32_t shard;      /* data shard, < data */
+    uint64_t offset;     /* first byte within the shard */
+    uint64_t len;        /* bytes, > 0, offset + len <= shard_len */
+    uint64_t src_offset; /* where the new bytes start in d_src */
+} shmr_ec_update;
+
+/* Applies nupdates updates (HOST array) to nblocks blocks addressed exactly as
+ * shmr_ec_encode_batch_dev; d_src: src_bytes bytes of DEVICE memory on
+ * `device` holding the new bytes.  d_src MUST NOT overlap the shards (the
+ * caller's contract: it is not checked, and the result of an overlap is
+ * undefined).  Any alignment of the bases, pitches, offset and src_offset and
+ * any parity >= 1 is accepted.
+ * Checked in this order, all before any device work: NULL rs
+ * (INVALID_ARGUMENT); nupdates == 0 or nblocks == 0 (OK, nothing enqueued);
+ * shard_len == 0 (EMPTY_SHARD); a NULL pointer (INVALID_ARGUMENT); per update
+ * block >= nblocks, shard >= data, len == 0, offset + len > shard_len or
+ * src_offset + len > src_bytes (INVALID_ARGUMENT); two updates whose byte
+ * ranges intersect in the same (block, shard) (INVALID_ARGUMENT: the order of
+ * two writes to one byte is not defined within a call); the device.
+ * Updates of different shards of a block over the same columns are fine: the
+ * call orders them itself (rounds, shmr_ec_update_rounds).
+ * Stream-ordered; after the first call on a device no blocking call of the
+ * library's own.  NOT capturable: a `stream` that is being captured into a
+ * graph is refused with INVALID_ARGUMENT and nothing is enqueued. */
+int shmr_ec_update_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pitch,
+                             size_t data_block_pitch, uint8_t* d_parity, size_t parity_shard_pitch,
+                             size_t parity_block_pitch, size_t nblocks, size_t shard_len,
+                             const shmr_ec_update* updates, size_t nupdates, const uint8_t* d_src,
+                             size_t src_bytes, int device, void* stream);
+
+/* Host only; for tests and tools (as shmr_ec_reconstruct_plan): the checks of
+ * shmr_ec_update_batch_dev on the list, then the round each update runs in
+ * (round_of: nupdates entries, or NULL) and the number of rounds.  Two updates
+ * of one block share a round only if their column ranges are disjoint (the
+ * kernel stores exactly the parity bytes of an update's columns), so pairwise
+ * disjoint ranges take 1 round and m shards of a block written over the same
+ * columns take m. */
+int shmr_ec_update_rounds(const shmr_ec_t* rs, const shmr_ec_update* updates, size_t nupdates,
+                          size_t nblocks, size_t shard_len, size_t src_bytes, uint32_t* round_of,
+                          uint32_t* nrounds);
+
 /* Reconstruct nblocks blocks in place.  All total shards of block b live at
  * d_shards + b*block_pitch + i*shard_pitch.  present is HOST memory,
  * nblocks x total flags (row-major).  Blocks may have different presence

@@ -64,6 +64,12 @@ SIGNATURES = [
     ("shmr_ec_scrub_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _sz, _sz,
       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_update_batch_dev", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _sz, _sz, ctypes.c_void_p, _sz,
+      ctypes.c_void_p, _sz, ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_update_rounds", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _sz, _sz, ctypes.POINTER(ctypes.c_uint32),
+      ctypes.POINTER(ctypes.c_uint32)]),
     ("shmr_ec_reconstruct_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_int, ctypes.c_int,
       ctypes.c_void_p]),
@@ -125,6 +131,12 @@ class KernelInfo(ctypes.Structure):
     """shmr_ec_kernel_info (include/shmr_ec.h)."""
     _fields_ = [("rows", ctypes.c_uint32), ("chunks", ctypes.c_uint32), ("mode", ctypes.c_uint32),
                 ("flags", ctypes.c_uint32), ("launches", ctypes.c_uint64)]
+
+
+class Update(ctypes.Structure):
+    """shmr_ec_update (include/shmr_ec.h)."""
+    _fields_ = [("block", ctypes.c_uint32), ("shard", ctypes.c_uint32), ("offset", ctypes.c_uint64),
+                ("len", ctypes.c_uint64), ("src_offset", ctypes.c_uint64)]
 
 _libs = {}
 _flavour = "tools" if os.environ.get("SHMR_EC_FLAVOUR") == "tools" else "product"

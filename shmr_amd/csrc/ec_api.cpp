@@ -965,6 +965,44 @@ int shmr_ec_scrub_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pi
     });
 }
 
+// ---- parity delta update: writes into device-resident blocks -------------------------
+int shmr_ec_update_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pitch, size_t data_block_pitch,
+                             uint8_t* d_parity, size_t parity_shard_pitch, size_t parity_block_pitch, size_t nblocks,
+                             size_t shard_len, const shmr_ec_update* updates, size_t nupdates, const uint8_t* d_src,
+                             size_t src_bytes, int device, void* stream) {
+    return guarded([&]() -> int {
+        if (!rs) return SHMR_EC_INVALID_ARGUMENT;
+        if (nupdates == 0) return SHMR_EC_OK;
+        Codec& c = *rs->codec;
+        shmr::update::Plan up;
+        auto check = [&] {
+            return arg_ok(d_data && d_parity && updates && d_src &&
+                          shmr::update::plan(updates, nupdates, nblocks, c.k(), shard_len, src_bytes, &up));
+        };
+        return batch_dev(nblocks, shard_len, device, check, [&] {
+            const core::Layout L{d_data, d_parity, data_block_pitch, data_shard_pitch, parity_block_pitch,
+                                 parity_shard_pitch, c.k()};
+            return core::update_on_device(c, device, L, up, d_src, static_cast<hipStream_t>(stream));
+        });
+    });
+}
+
+int shmr_ec_update_rounds(const shmr_ec_t* rs, const shmr_ec_update* updates, size_t nupdates, size_t nblocks,
+                          size_t shard_len, size_t src_bytes, uint32_t* round_of, uint32_t* nrounds) {
+    return guarded_light([&]() -> int {
+        if (!rs || !nrounds) return SHMR_EC_INVALID_ARGUMENT;
+        *nrounds = 0;
+        if (nupdates == 0 || nblocks == 0) return SHMR_EC_OK;
+        if (shard_len == 0) return SHMR_EC_EMPTY_SHARD;
+        shmr::update::Plan up;
+        if (!updates || !shmr::update::plan(updates, nupdates, nblocks, rs->codec->k(), shard_len, src_bytes, &up, false))
+            return SHMR_EC_INVALID_ARGUMENT;
+        if (round_of) std::copy(up.round_of.begin(), up.round_of.end(), round_of);
+        *nrounds = up.nrounds;
+        return SHMR_EC_OK;
+    });
+}
+
 int shmr_ec_reconstruct_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard_pitch, size_t block_pitch,
                                   const uint8_t* present, size_t nblocks, size_t shard_len, int data_only, int device,
                                   void* stream) {

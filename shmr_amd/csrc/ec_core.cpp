@@ -1166,6 +1166,83 @@ int locate_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
     return SHMR_EC_OK;
 }
 
+// ===========================================================================
+// Parity delta update.  The pieces come in round order; a table chunk holds
+// up to kUpdateTablePieces of them (one ring slot) and fewer than 2^31 tiles,
+// and the pieces of each round in it are one launch.  Two pieces of one round
+// in different chunks run in different launches, which is as good: rounds only
+// keep pieces with intersecting footprints out of one launch.
+// ===========================================================================
+int update_on_device(Codec& c, int dev, const Layout& L, const update::Plan& up, const uint8_t* d_src,
+                     hipStream_t stream) {
+    static_assert(kUpdateTablePieces * sizeof(update::DevPiece) == UploadRing::kSlotBytes, "one ring slot per chunk");
+    int rc = device_init(dev, stream);
+    if (rc) return rc;
+    bool capturing = false;
+    if ((rc = capture_state(stream, &capturing))) return rc;
+    if (capturing) return SHMR_EC_INVALID_ARGUMENT;
+    Plan& plan = *c.encode_plan();
+    const uint8_t* dplan = nullptr;
+    rc = plan_on_device(plan, dev, stream, false, &dplan);
+    if (rc) return rc;
+    // 16-byte accesses: anywhere where the device serves unaligned ones, else
+    // only where every address of the piece is aligned (its columns are)
+    const bool uvec = unaligned_vector(dev), base16 = layout_aligned16(L);
+    kern::UpdateArgs u{};
+    u.data = const_cast<uint8_t*>(L.in_base);
+    u.parity = L.out_base;
+    u.src = d_src;
+    u.tabs = dplan + plan_tab_off(plan.k, plan.m);
+    u.data_bpitch = L.in_bpitch;
+    u.data_spitch = L.in_spitch;
+    u.par_bpitch = L.out_bpitch;
+    u.par_spitch = L.out_spitch;
+    u.p = plan.m;
+    const std::vector<update::Piece>& ps = up.pieces;
+    for (size_t c0 = 0; c0 < ps.size();) {
+        size_t cnt = 0;
+        uint64_t tiles = 0;
+        while (c0 + cnt < ps.size() && cnt < kUpdateTablePieces) {
+            const uint64_t t = update::piece_tiles(ps[c0 + cnt].len);
+            if (tiles + t > 0x7fffffffull) break;
+            tiles += t;
+            ++cnt;
+        }
+        rc = with_table(
+            dev, stream, cnt * sizeof(update::DevPiece),
+            [&](uint8_t* h) {
+                update::DevPiece* dp = reinterpret_cast<update::DevPiece*>(h);
+                uint32_t tile0 = 0;
+                for (size_t i = 0; i < cnt; ++i) {
+                    const update::Piece& p = ps[c0 + i];
+                    const bool vec = p.vec && (uvec || (base16 && aligned16(uintptr_t(d_src) + p.src)));
+                    dp[i] = update::DevPiece{p.col, p.src, p.block, p.len, p.shard | (vec ? update::kVecFlag : 0u), tile0};
+                    tile0 += update::piece_tiles(p.len);
+                }
+            },
+            [&](const uint8_t* d) -> int {
+                uint32_t tile0 = 0;
+                for (size_t i = 0; i < cnt;) {   // the chunk's pieces of one round
+                    size_t j = i;
+                    uint32_t nt = 0;
+                    for (; j < cnt && ps[c0 + j].round == ps[c0 + i].round; ++j) nt += update::piece_tiles(ps[c0 + j].len);
+                    u.pieces = reinterpret_cast<const update::DevPiece*>(d) + i;
+                    u.npieces = uint32_t(j - i);
+                    u.tile_base = tile0;
+                    u.ntiles = nt;
+                    count_device(dev, kDevLaunches);
+                    SHMR_HIP_TRY(kern::launch_update(u, stream));
+                    tile0 += nt;
+                    i = j;
+                }
+                return SHMR_EC_OK;
+            });
+        if (rc) return rc;
+        c0 += cnt;
+    }
+    return SHMR_EC_OK;
+}
+
 int validate_presence(const Codec& c, const uint8_t* present, uint64_t nblocks) {
     const unsigned k = c.k(), t = k + c.p();
     for (uint64_t b = 0; b < nblocks; ++b) {

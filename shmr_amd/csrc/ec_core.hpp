@@ -17,6 +17,7 @@
 #include "gf256.hpp"
 #include "gf_apply.hpp"
 #include "shmr_ec.h"
+#include "update_plan.hpp"
 
 namespace shmr {
 namespace core {
@@ -284,6 +285,17 @@ int verify_chunks(unsigned rows);
 size_t locate_work_bytes(const Codec& c, uint64_t nblocks);
 int locate_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint64_t len, uint32_t* d_mismatch,
                      int32_t* d_located, uint32_t* d_cand, hipStream_t stream);
+// Parity delta update (shmr_ec_update_batch_dev): the planned pieces `up`
+// (update_plan.hpp, validated by the caller) applied to blocks laid out per
+// `L` as for encode_on_device (L.in_base: the data, written here too), the new
+// bytes read from d_src.  The piece table travels through the upload ring in
+// chunks of kUpdateTablePieces; behind each chunk one launch per round present
+// in it, rounds in ascending order on `stream`.  Stream-ordered, no blocking
+// call after device init; a stream that is being captured is refused
+// (INVALID_ARGUMENT, nothing enqueued).
+constexpr size_t kUpdateTablePieces = 256 * 1024 / 32;   // UploadRing::kSlotBytes / sizeof(update::DevPiece)
+int update_on_device(Codec& c, int dev, const Layout& L, const update::Plan& up, const uint8_t* d_src,
+                     hipStream_t stream);
 // The blocks slots[0 .. n) (ascending, distinct) of a single-plan launch set.
 int launch_slots(Plan& plan, int dev, const Layout& L, const uint64_t* slots, uint64_t n, uint64_t len,
                  hipStream_t stream, OpClass op);

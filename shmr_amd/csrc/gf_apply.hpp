@@ -6,6 +6,9 @@
 #include <cstdint>
 
 namespace shmr {
+namespace update {
+struct DevPiece;   // update_plan.hpp
+}
 namespace kern {
 
 constexpr int kThreads = 256;                          // lanes per workgroup (4 waves)
@@ -312,6 +315,28 @@ hipError_t launch_locate_preset(uint32_t* cand, uint64_t nblk, unsigned k, hipSt
 // located[b] = locate::resolve(mismatch[b], cand + b * words, k, p) (locate_plan.hpp), b < nblk.
 hipError_t launch_locate_resolve(const uint32_t* mismatch, const uint32_t* cand, int32_t* located, uint64_t nblk,
                                  unsigned k, unsigned p, hipStream_t stream);
+
+// The parity delta update kernel (gf_update.hip; shmr_ec_update_batch_dev):
+// one launch over pieces [0, npieces) of a piece table (update_plan.hpp
+// DevPiece, device memory), all of one round: no two of them store to the same
+// parity byte.  One workgroup per 4 KiB tile of a piece; tile_base = the first
+// piece's tile0, ntiles = the tiles of these pieces (< 2^31).  tabs: the
+// PermTab[k][p] tables of the codec's encode plan image (entry j * p + r).
+// Stores bytes [col, col + len) of the piece's data shard and of every parity
+// row of its block, nothing else; loads the same bytes and len bytes of src.
+// A piece without kVecFlag moves byte by byte: the edges, and every piece whose
+// addresses are off 16-byte alignment on a device without unaligned vector
+// access.  Not part of kernel_inventory.
+struct UpdateArgs {
+    uint8_t* data;
+    uint8_t* parity;
+    const uint8_t* src;
+    const uint8_t* tabs;
+    const update::DevPiece* pieces;
+    uint64_t data_bpitch, data_spitch, par_bpitch, par_spitch;
+    uint32_t p, npieces, tile_base, ntiles;
+};
+hipError_t launch_update(const UpdateArgs& u, hipStream_t stream);
 
 // The submission queue's completion mark (submit.cpp): a one-wave kernel on
 // `stream` that stores `seq` to `word` -- pinned host memory, a system-scope

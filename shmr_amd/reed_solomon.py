@@ -326,6 +326,89 @@ class ReedSolomon:
         data, parity = self._split_shards(shards)
         return self.scrub_batch_dev(data, parity, shard_len=shard_len, device=device)
 
+    # -- parity delta update: writes into device-resident blocks -------------------
+    _UPDATE_DTYPE = np.dtype([("block", "<u4"), ("shard", "<u4"), ("offset", "<u8"), ("len", "<u8"),
+                              ("src_offset", "<u8")], align=True)
+
+    @classmethod
+    def _update_array(cls, updates) -> np.ndarray:
+        """``updates`` -> a contiguous array of ``shmr_ec_update``: a sequence of
+        ``(block, shard, offset, length, src_offset)`` or an ``(n, 5)`` integer
+        array.  Values the C fields cannot hold are an ``InvalidArgument``."""
+        if isinstance(updates, np.ndarray):
+            if updates.dtype.kind not in "iu":
+                raise TypeError("updates must be an integer array")
+            if updates.size and (updates.ndim != 2 or updates.shape[1] != 5):
+                raise TypeError("updates must be an (n, 5) array")
+            a = updates.reshape(-1, 5)
+            if a.dtype.kind == "i" and (a < 0).any():
+                raise Error(-100)                                # InvalidArgument
+            a = a.astype(np.uint64)
+            if (a[:, :2] >> np.uint64(32)).any():
+                raise Error(-100)
+            out = np.zeros(len(a), dtype=cls._UPDATE_DTYPE)
+            for i, name in enumerate(cls._UPDATE_DTYPE.names):
+                out[name] = a[:, i]
+            return out
+        else:
+            rows = [tuple(row) for row in updates]
+        out = np.zeros(len(rows), dtype=cls._UPDATE_DTYPE)
+        for i, row in enumerate(rows):
+            if len(row) != 5 or not all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in row):
+                raise TypeError("an update is five integers: (block, shard, offset, length, src_offset)")
+            b, s, off, n, src = (int(x) for x in row)
+            if not (0 <= b < 1 << 32 and 0 <= s < 1 << 32 and all(0 <= x < 1 << 64 for x in (off, n, src))):
+                raise Error(-100)                                # InvalidArgument
+            out[i] = (b, s, off, n, src)
+        return out
+
+    def update_rounds(self, updates, nblocks: int, shard_len: int, src_bytes: int):
+        """``shmr_ec_update_rounds`` (host only): the checks ``update_batch_dev``
+        makes on the list, then ``(round_of, nrounds)``: a numpy uint32 array with
+        the round each update runs in, and the number of rounds.  Updates of one
+        block share a round only if their column ranges are disjoint."""
+        ua = self._update_array(updates)
+        round_of = np.zeros(len(ua), dtype=np.uint32)
+        nrounds = ctypes.c_uint32(0)
+        _check(self._L.shmr_ec_update_rounds(self._h, ctypes.c_void_p(ua.ctypes.data), len(ua), nblocks, shard_len,
+                                             src_bytes, round_of.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                             ctypes.byref(nrounds)))
+        return round_of, int(nrounds.value)
+
+    def update_batch_dev(self, data, parity, updates, src, shard_len: Optional[int] = None,
+                         device: Optional[int] = None) -> None:
+        """Writes into device-resident blocks and keeps their parity valid
+        (``shmr_ec_update_batch_dev``): data and parity as ``encode_batch_dev``
+        takes them (same tensor forms, same checks in the same order); ``src`` a
+        1-D uint8 tensor on the same GPU holding the new bytes, which must not
+        overlap data or parity.  For every ``(block, shard, offset, length,
+        src_offset)`` of ``updates`` bytes [offset, offset + length) of that data
+        shard become ``src[src_offset : src_offset + length]`` and every parity
+        row changes by C[r][shard] (x) (old ^ new) on those columns; nothing
+        else is written.  Two updates must not intersect in one (block, shard).
+        Enqueued on torch's current stream; not for graph capture (the native
+        call refuses a stream that is being captured)."""
+        import torch
+        B, dsp, dbp, psp, pbp, L = self._device_regions(data, parity, shard_len, "update_batch_dev")
+        if (not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.dim() != 1
+                or (src.numel() > 1 and src.stride(0) != 1)):
+            raise TypeError("src must be a 1-D contiguous torch.uint8 tensor")
+        if src.device != data.device:
+            raise TypeError(f"src must be on {data.device}")
+        ua = self._update_array(updates)
+        dev, stream = self._stream_and_device(data)
+        dev = dev if device is None else int(device)
+        _check(self._L.shmr_ec_update_batch_dev(self._h, ctypes.c_void_p(data.data_ptr()), dsp, dbp,
+                                                ctypes.c_void_p(parity.data_ptr()), psp, pbp, B, L,
+                                                ctypes.c_void_p(ua.ctypes.data), len(ua),
+                                                ctypes.c_void_p(src.data_ptr()), src.numel(), dev, stream))
+
+    def update_shards_dev(self, shards, updates, src, shard_len: Optional[int] = None,
+                          device: Optional[int] = None) -> None:
+        """``update_batch_dev`` of one ``[B, k + p, pitch]`` tensor, as ``verify_shards_dev``."""
+        data, parity = self._split_shards(shards)
+        self.update_batch_dev(data, parity, updates, src, shard_len=shard_len, device=device)
+
     # -- device-resident batches (torch tensors on the GPU) ------------------------
     @staticmethod
     def _check_batch_tensor(t, rows: int, shard_pitch: int, shard_len: int) -> None:
