@@ -21,21 +21,16 @@ import numpy as np
 import pytest
 
 import shmr_amd
+from locate_cases import GUARD, SENT, HostCase
 from locate_ref import CLEAN, NONE, locate_ref
-from oracle import c_oracle
 
 pytestmark = pytest.mark.gpu
 
 CODES = [(4, 2), (8, 3), (10, 4), (5, 5), (3, 9)]       # RS(5,5), RS(3,9): parity rows beyond the first row group
 LENGTHS = [16, 1000, 4096 + 48, 8192 + 48]
 B = 5
-GUARD, SENT = 256, 0xC3
 WORD_SENT = 0x5A5A5A5A
 INVALID = -100
-
-
-def _pitch(L):
-    return (L // 64 + 1) * 64            # above len, a multiple of 64
 
 
 def damage_of(k, p, L):
@@ -50,69 +45,47 @@ def damage_of(k, p, L):
     return d, [CLEAN, 0, k - 1, k + p - 1, NONE if p >= 3 else k]
 
 
-class Case:
-    """Codewords of one (k, p, L) in the guarded two-region device layout; `odd`
-    puts both regions at an odd byte offset."""
+class Case(HostCase):
+    """Codewords of one (k, p, L) in the guarded two-region device layout
+    (locate_cases.HostCase, nblk blocks); `odd` puts both regions at an odd
+    byte offset."""
 
-    def __init__(self, k, p, L, gpu, seed, odd=False):
+    def __init__(self, k, p, L, gpu, seed, odd=False, nblk=B, pitch=None):
         import torch
-        self.k, self.p, self.L, self.pitch, self.gpu = k, p, L, _pitch(L), gpu
-        rng = np.random.default_rng(seed)
-        pitch = self.pitch
-        self.data_off = GUARD + (1 if odd else 0)
-        self.par_off = self.data_off + B * k * pitch + GUARD
-        total = self.par_off + B * p * pitch + GUARD
-        img = np.full(total, SENT, np.uint8)
-        d = img[self.data_off:self.data_off + B * k * pitch].reshape(B, k, pitch)
-        q = img[self.par_off:self.par_off + B * p * pitch].reshape(B, p, pitch)
-        d[:] = rng.integers(0, 256, d.shape, dtype=np.uint8)       # padding past len: random, not a codeword
-        q[:] = rng.integers(0, 256, q.shape, dtype=np.uint8)
-        par = np.zeros((B, p, L), np.uint8)
-        c_oracle.encode_batch(k, p, np.ascontiguousarray(d[:, :, :L]), par, B, L, 8)
-        q[:, :, :L] = par
-        self.pristine = img
-        self.rng = rng
+        super().__init__(k, p, L, seed, nblk=nblk, odd=odd, pitch=pitch)
+        self.gpu = gpu
         self.rs = shmr_amd.ReedSolomon(k, p)
-        self.words = torch.empty(B + 2, dtype=torch.int32, device=gpu)
-        self.located = torch.empty(B + 2, dtype=torch.int32, device=gpu)
-        self.need = self.rs.locate_work_size(B)
+        self.words = torch.empty(nblk + 2, dtype=torch.int32, device=gpu)
+        self.located = torch.empty(nblk + 2, dtype=torch.int32, device=gpu)
+        self.need = self.rs.locate_work_size(nblk)
         self.work = torch.empty(self.need + 2 * GUARD, dtype=torch.uint8, device=gpu)
-        self.load(img)
+        self.load(self.pristine)
 
     def load(self, img):
         """Puts a host image on the device: self.img is what the device holds."""
         import torch
-        k, p, pitch = self.k, self.p, self.pitch
+        B, k, p, pitch = self.B, self.k, self.p, self.pitch
         self.img = img.copy()
         self.buf = torch.from_numpy(self.img.copy()).to(self.gpu)
         self.data = torch.as_strided(self.buf, (B, k, pitch), (k * pitch, pitch, 1), self.data_off)
         self.parity = torch.as_strided(self.buf, (B, p, pitch), (p * pitch, pitch, 1), self.par_off)
 
-    def regions(self, img):
-        """(data [B, k, pitch], parity [B, p, pitch]) views of a host image."""
-        k, p, pitch = self.k, self.p, self.pitch
-        return (img[self.data_off:self.data_off + B * k * pitch].reshape(B, k, pitch),
-                img[self.par_off:self.par_off + B * p * pitch].reshape(B, p, pitch))
-
-    def damaged(self, damage):
-        img = self.pristine.copy()
-        d, q = self.regions(img)
-        for b, s, col, x in damage:
-            (d if s < self.k else q)[b, s if s < self.k else s - self.k, col] ^= x
-        return img
-
     def reference(self):
         """locate_ref of every block of the host copy of what the device holds."""
         d, q = self.regions(self.img)
-        return [locate_ref(self.k, self.p, d[b, :, :self.L], q[b, :, :self.L]) for b in range(B)]
+        return [locate_ref(self.k, self.p, d[b, :, :self.L], q[b, :, :self.L]) for b in range(self.B)]
 
-    def locate(self, work_bytes=None, rs=None):
+    def locate(self, work_bytes=None, rs=None, work_fill=SENT):
         """One shmr_ec_locate_batch_dev into the guarded result arrays ->
-        (status, words [B] uint32, located [B] int32); sentinels checked."""
+        (status, words [B] uint32, located [B] int32); sentinels checked.
+        `work_fill`: what the scratch between its guards holds before the call."""
         import torch
+        B = self.B
         self.words.fill_(WORD_SENT)
         self.located.fill_(WORD_SENT)
         self.work.fill_(SENT)
+        if work_fill != SENT:
+            self.work[GUARD:GUARD + self.need].fill_(work_fill)
         v = ctypes.c_void_p
         rs = rs or self.rs
         rc = rs._L.shmr_ec_locate_batch_dev(
