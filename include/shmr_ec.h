@@ -399,6 +399,64 @@ int shmr_ec_reconstruct_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard
                                   size_t block_pitch, const uint8_t* present, size_t nblocks,
                                   size_t shard_len, int data_only, int device, void* stream);
 
+/* ---- checked reconstruct: verify the spare shards while rebuilding ----------- *
+ * shmr_ec_reconstruct_batch_dev reads the first `data` present shards of a
+ * block and never looks at the other present ones; shmr_ec_verify_batch_dev
+ * needs every shard present.  This call does both in one pass over a block
+ * with absent shards, so damage in a surviving shard is reported instead of
+ * being rebuilt into the absent ones unnoticed.  Per block, with np >= data
+ * present shards:
+ *   - inputs: the first `data` present shards in index order (the crate's rule);
+ *   - rebuilt: exactly the shards, rows and bytes of
+ *     shmr_ec_reconstruct_batch_dev for this pattern and data_only;
+ *   - surplus: the np - data present shards behind the inputs (always parity
+ *     shards; with every shard present, the whole parity).  Each surplus shard
+ *     data + r is recomputed from the inputs and compared on [0, shard_len).
+ * d_mismatch[b], b the block's index in the batch: 0 if every surplus shard
+ * agrees (or there is none: np == data), else bit min(r, 31) for each surplus
+ * parity row r that differs -- the encoding of shmr_ec_verify_batch_dev, whose
+ * word a block with every shard present gets exactly (nothing of it is
+ * written).  The code is MDS: one damaged input byte makes EVERY surplus row
+ * differ (the word is shmr_ec_checked_rows of the pattern), damage in surplus
+ * shard data + r only row r.  Rebuilt bytes are written whether or not the
+ * word ends up non-zero: the word says they are suspect.
+ * Addressing and `present` exactly as shmr_ec_reconstruct_batch_dev (HOST
+ * flags, nblocks x total, patterns may differ per block, every block validated
+ * before any launch); absent slots are never read.  d_mismatch: nblocks uint32
+ * words of DEVICE memory, 4-byte aligned, overwritten (the zeroing is part of
+ * the enqueued work).
+ * Checked in this order, all before any device work: NULL rs
+ * (INVALID_ARGUMENT); nblocks == 0 (OK, nothing enqueued); shard_len == 0
+ * (EMPTY_SHARD); a NULL pointer or unknown flag bits (INVALID_ARGUMENT); a
+ * block with fewer than `data` present (TOO_FEW_SHARDS_PRESENT); the device.
+ * Stream-ordered, no host readback.  NOT capturable: a `stream` that is being
+ * captured into a graph is refused with INVALID_ARGUMENT and nothing is
+ * enqueued.  Counted under SHMR_EC_DEV_BLOCKS_VERIFIED (every block),
+ * SHMR_EC_DEV_BLOCKS_RECONSTRUCTED (blocks with an absent shard) and
+ * SHMR_EC_DEV_LAUNCHES (per pattern, one per group of <= 4 plan rows). */
+#define SHMR_EC_CHECK_DATA_ONLY 1  /* as data_only of shmr_ec_reconstruct_batch_dev */
+#define SHMR_EC_CHECK_NO_REBUILD 2 /* compare only: no shard is written ("verify with erasures") */
+int shmr_ec_reconstruct_checked_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard_pitch,
+                                          size_t block_pitch, const uint8_t* present,
+                                          size_t nblocks, size_t shard_len, int flags,
+                                          uint32_t* d_mismatch, int device, void* stream);
+
+/* Host only; for tests and tools (as shmr_ec_reconstruct_plan): the bit mask
+ * (bit min(r, 31)) of the parity rows the check compares for one presence
+ * pattern.  Counts as shmr_ec_reconstruct_plan (TOO_FEW / TOO_MANY_SHARDS,
+ * TOO_FEW_SHARDS_PRESENT). */
+int shmr_ec_checked_rows(const shmr_ec_t* rs, const uint8_t* present, size_t nshards, uint32_t* rows);
+
+/* Host only; for tests and tools: the plan the checked reconstruct runs for a
+ * presence pattern and `flags`, in the shape of shmr_ec_reconstruct_plan.
+ * Rows [0, *n_store) are stored to shard out_idx[m] (the rows of
+ * shmr_ec_reconstruct_plan, verbatim); rows [*n_store, *n_store + *n_check)
+ * are compared with the stored bytes of surplus shard out_idx[m].
+ * out_idx holds total entries, out_rows at least (*n_store + *n_check) * data. */
+int shmr_ec_checked_plan(shmr_ec_t* rs, const uint8_t* present, size_t nshards, int flags,
+                         uint16_t* in_idx, uint16_t* out_idx, uint8_t* out_rows,
+                         size_t out_rows_len, uint32_t* n_store, uint32_t* n_check);
+
 /* Reconstruct with the crate's memory semantics: every absent shard is
  * rebuilt into a buffer of its own (reed_solomon_erasure allocates
  * vec![0; len] for each None, called at src/vfs/block.rs:556-565; load_block

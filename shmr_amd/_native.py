@@ -73,6 +73,13 @@ SIGNATURES = [
     ("shmr_ec_reconstruct_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_int, ctypes.c_int,
       ctypes.c_void_p]),
+    ("shmr_ec_reconstruct_checked_batch_dev", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+      ctypes.c_void_p]),
+    ("shmr_ec_checked_rows", ctypes.c_int, [ctypes.c_void_p, _u8p, _sz, ctypes.POINTER(ctypes.c_uint32)]),
+    ("shmr_ec_checked_plan", ctypes.c_int,
+     [ctypes.c_void_p, _u8p, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(ctypes.c_uint16),
+      _u8p, _sz, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     ("shmr_ec_reconstruct_batch_dev_out", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_int, ctypes.c_void_p, _sz, _sz,
       ctypes.c_int, ctypes.c_void_p]),

@@ -1018,6 +1018,79 @@ int shmr_ec_reconstruct_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard
     });
 }
 
+// ---- checked reconstruct: the surplus shards compared while rebuilding ---------------
+int shmr_ec_reconstruct_checked_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard_pitch, size_t block_pitch,
+                                          const uint8_t* present, size_t nblocks, size_t shard_len, int flags,
+                                          uint32_t* d_mismatch, int device, void* stream) {
+    return guarded([&]() -> int {
+        if (!rs) return SHMR_EC_INVALID_ARGUMENT;
+        Codec& c = *rs->codec;
+        const int known = SHMR_EC_CHECK_DATA_ONLY | SHMR_EC_CHECK_NO_REBUILD;
+        const bool given = d_shards && present && d_mismatch && uintptr_t(d_mismatch) % alignof(uint32_t) == 0 &&
+                           (flags & ~known) == 0;
+        // (no launch on a bad batch)
+        auto check = [&] { return given ? core::validate_presence(c, present, nblocks) : arg_ok(false); };
+        return batch_dev(nblocks, shard_len, device, check, [&] {
+            return core::checked_on_device(c, device, d_shards, shard_pitch, block_pitch, present, nblocks, shard_len,
+                                           (flags & SHMR_EC_CHECK_DATA_ONLY) != 0,
+                                           (flags & SHMR_EC_CHECK_NO_REBUILD) != 0, d_mismatch,
+                                           static_cast<hipStream_t>(stream));
+        });
+    });
+}
+
+// The crate's checks of one presence pattern for the host-only exports below.
+static int check_pattern(const shmr_ec_t* rs, const uint8_t* present, size_t nshards) {
+    const unsigned k = rs->codec->k(), t = k + rs->codec->p();
+    if (nshards < t) return SHMR_EC_TOO_FEW_SHARDS;
+    if (nshards > t) return SHMR_EC_TOO_MANY_SHARDS;
+    unsigned np = 0;
+    for (unsigned i = 0; i < t; ++i) np += present[i] ? 1 : 0;
+    return np < k ? SHMR_EC_TOO_FEW_SHARDS_PRESENT : SHMR_EC_OK;
+}
+
+int shmr_ec_checked_rows(const shmr_ec_t* rs, const uint8_t* present, size_t nshards, uint32_t* rows) {
+    return guarded_light([&]() -> int {
+        if (!rs || !present || !rows) return SHMR_EC_INVALID_ARGUMENT;
+        const int rc = check_pattern(rs, present, nshards);
+        if (rc) return rc;
+        // the present shards behind the first k present ones: always parity
+        const unsigned k = rs->codec->k(), t = k + rs->codec->p();
+        uint32_t mask = 0;
+        unsigned seen = 0;
+        for (unsigned i = 0; i < t; ++i) {
+            if (!present[i]) continue;
+            if (seen++ >= k) mask |= 1u << std::min(i - k, 31u);
+        }
+        *rows = mask;
+        return SHMR_EC_OK;
+    });
+}
+
+int shmr_ec_checked_plan(shmr_ec_t* rs, const uint8_t* present, size_t nshards, int flags, uint16_t* in_idx,
+                         uint16_t* out_idx, uint8_t* out_rows, size_t out_rows_len, uint32_t* n_store,
+                         uint32_t* n_check) {
+    return guarded_light([&]() -> int {
+        if (!rs || !present || !in_idx || !out_idx || !out_rows || !n_store || !n_check) return SHMR_EC_INVALID_ARGUMENT;
+        if ((flags & ~(SHMR_EC_CHECK_DATA_ONLY | SHMR_EC_CHECK_NO_REBUILD)) != 0) return SHMR_EC_INVALID_ARGUMENT;
+        const int rc = check_pattern(rs, present, nshards);
+        if (rc) return rc;
+        const unsigned k = rs->codec->k(), t = k + rs->codec->p();
+        std::vector<uint8_t> pr(present, present + t);
+        auto plan = rs->codec->checked_plan(pr, (flags & SHMR_EC_CHECK_DATA_ONLY) != 0,
+                                            (flags & SHMR_EC_CHECK_NO_REBUILD) != 0);
+        if (out_rows_len < size_t(plan->m) * k) return SHMR_EC_INVALID_ARGUMENT;
+        std::memcpy(in_idx, plan->in_idx.data(), 2 * size_t(k));
+        if (plan->m) {   // (exactly k present and nothing rebuilt: an empty plan)
+            std::memcpy(out_idx, plan->out_idx.data(), 2 * size_t(plan->m));
+            std::memcpy(out_rows, plan->rows.d.data(), size_t(plan->m) * k);
+        }
+        *n_store = plan->m - plan->n_check;
+        *n_check = plan->n_check;
+        return SHMR_EC_OK;
+    });
+}
+
 int shmr_ec_reconstruct_batch_dev_out(shmr_ec_t* rs, const uint8_t* d_shards, size_t shard_pitch, size_t block_pitch,
                                       const uint8_t* present, size_t nblocks, size_t shard_len, int data_only,
                                       uint8_t* d_out, size_t out_shard_pitch, size_t out_block_pitch, int device,

@@ -1389,6 +1389,98 @@ int reconstruct_on_device(Codec& c, int dev, const Layout& L, const uint8_t* pre
 }
 
 // ===========================================================================
+// Checked reconstruct.  Blocks are grouped by presence pattern as above; every
+// pattern is a single-plan launch set of its checked plan (stored rows, then
+// compare rows), split per row group as a verify's launches (launch_split, 4 KiB
+// tiles).  The store / compare boundary of a group is nstore = the stored rows
+// that fall into it; a compare row's bit is its parity row index.
+// ===========================================================================
+int checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch, uint64_t block_pitch,
+                      const uint8_t* present, uint64_t nblocks, uint64_t len, bool data_only, bool no_rebuild,
+                      uint32_t* d_mismatch, hipStream_t stream) {
+    const unsigned k = c.k(), t = k + c.p();
+    int rc = device_init(dev, stream);
+    if (rc) return rc;
+    // Not inside a graph capture (shmr_ec.h): refused before anything is enqueued.
+    bool capturing = false;
+    if ((rc = capture_state(stream, &capturing))) return rc;
+    if (capturing) return SHMR_EC_INVALID_ARGUMENT;
+    if (nblocks == 0) return SHMR_EC_OK;
+    if (nblocks > 0xffffffffull) return SHMR_EC_INVALID_ARGUMENT;   // block lists are 32-bit
+    std::map<std::vector<uint8_t>, std::vector<uint32_t>> groups;   // pattern -> blocks
+    uint64_t degraded = 0;
+    for (uint64_t b = 0; b < nblocks; ++b) {
+        const uint8_t* pr = present + b * t;
+        std::vector<uint8_t> key(t);
+        unsigned np = 0;
+        for (unsigned i = 0; i < t; ++i) np += (key[i] = pr[i] ? 1 : 0);
+        if (np < k) return SHMR_EC_TOO_FEW_SHARDS_PRESENT;
+        degraded += np != t ? 1 : 0;
+        groups[key].push_back(uint32_t(b));
+    }
+    SHMR_HIP_TRY(hipMemsetAsync(d_mismatch, 0, size_t(nblocks) * sizeof(uint32_t), stream));
+    count_device(dev, kDevBlocksVerified, nblocks);
+    count_device(dev, kDevBlocksReconstructed, degraded);
+    const Layout L{d_shards, d_shards, block_pitch, shard_pitch, block_pitch, shard_pitch, 0};
+    const bool aligned = layout_aligned16(L) || unaligned_vector(dev);
+    for (auto& g : groups) {
+        const std::shared_ptr<Plan> planp = c.checked_plan(g.first, data_only, no_rebuild);
+        Plan& plan = *planp;
+        if (plan.m == 0) continue;   // exactly k present and nothing to rebuild
+        const uint8_t* dplan = nullptr;
+        rc = plan_on_device(plan, dev, stream, false, &dplan);
+        if (rc) return rc;
+        const uint32_t m_store = plan.m - plan.n_check;
+        kern::ApplyArgs a = apply_args(L, plan, dplan, len);
+        // the row groups of the pattern over the blocks `a` names
+        auto launch_groups = [&]() -> int {
+            for (uint32_t row0 = 0; row0 < plan.m; row0 += kern::kMaxRowsPerLaunch) {
+                const uint32_t rows = std::min<uint32_t>(kern::kMaxRowsPerLaunch, plan.m - row0);
+                const uint32_t nstore = m_store > row0 ? std::min(m_store - row0, rows) : 0;
+                uint32_t bits[kern::kMaxRowsPerLaunch] = {};
+                for (uint32_t r = nstore; r < rows; ++r) bits[r] = std::min<uint32_t>(plan.out_idx[row0 + r] - k, 31);
+                count_device(dev, kDevLaunches);
+                a.row0 = row0;
+                const int lrc = launch_split(a, len, kern::tile_bytes(1), aligned ? 0 : -1, aligned ? 1 : 2,
+                                             [&](int mode) -> int {
+                                                 SHMR_HIP_TRY(kern::launch_check(a, d_mismatch, rows, nstore, bits, mode,
+                                                                                 stream));
+                                                 return SHMR_EC_OK;
+                                             });
+                if (lrc) return lrc;
+            }
+            return SHMR_EC_OK;
+        };
+        const std::vector<uint32_t>& blocks = g.second;
+        bool arith = true;
+        const uint64_t stride = blocks.size() > 1 ? uint64_t(blocks[1]) - blocks[0] : 1;
+        for (size_t i = 1; arith && i < blocks.size(); ++i) arith = uint64_t(blocks[i]) - blocks[i - 1] == stride;
+        if (arith) {
+            a.blk_first = blocks[0];
+            a.blk_stride = stride;
+            a.nblk = blocks.size();
+            if ((rc = launch_groups())) return rc;
+            continue;
+        }
+        // an uploaded block list, a ring slot per chunk
+        const size_t per = UploadRing::kSlotBytes / sizeof(uint32_t);
+        for (size_t c0 = 0; c0 < blocks.size(); c0 += per) {
+            const size_t cnt = std::min(per, blocks.size() - c0);
+            rc = with_table(
+                dev, stream, cnt * sizeof(uint32_t),
+                [&](uint8_t* h) { std::memcpy(h, blocks.data() + c0, cnt * sizeof(uint32_t)); },
+                [&](const uint8_t* d) {
+                    a.blk_list = reinterpret_cast<const uint32_t*>(d);
+                    a.nblk = cnt;
+                    return launch_groups();
+                });
+            if (rc) return rc;
+        }
+    }
+    return SHMR_EC_OK;
+}
+
+// ===========================================================================
 // Upload ring
 // ===========================================================================
 UploadRing* UploadRing::for_device(int dev, int* rc, Kind kind) {

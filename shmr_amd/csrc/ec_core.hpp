@@ -313,6 +313,23 @@ int reconstruct_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_p
 int reconstruct_on_device(Codec& c, int dev, const Layout& L, const uint8_t* present, uint64_t nblocks, uint64_t len,
                           bool data_only, hipStream_t stream, const uint64_t* slots = nullptr);
 
+// Checked reconstruct in place (shmr_ec_reconstruct_checked_batch_dev): the
+// layout and `present` of reconstruct_on_device above, validated by the caller.
+// d_mismatch[b] (device memory, 4-byte aligned; b the block's index in the
+// batch) is zeroed on `stream`; then per presence pattern the codec's checked
+// plan (gf256.hpp checked_plan) runs in one pass per group of <= 4 rows: the
+// rebuilt shards are stored as reconstruct_on_device stores them (none with
+// no_rebuild), and bit min(r, 31) is ORed into the block's word for every
+// surplus parity shard k + r whose stored bytes differ from the recomputed
+// ones in [0, len).  One launch set per pattern (no multi-plan table): an
+// arithmetic block sequence by first / stride, any other through an uploaded
+// block list, a ring slot per chunk.  Stream-ordered; a stream that is being
+// captured is refused (INVALID_ARGUMENT, nothing enqueued).  Counts every
+// block as verified, those with an absent shard also as reconstructed.
+int checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch, uint64_t block_pitch,
+                      const uint8_t* present, uint64_t nblocks, uint64_t len, bool data_only, bool no_rebuild,
+                      uint32_t* d_mismatch, hipStream_t stream);
+
 // A shard-pointer table call (ptrs.cpp): tab[b * total + i] is the device
 // address of shard i of block b (0 for a shard the call does not touch),
 // validated by the caller.  A table on a slot lattice runs the strided kernels

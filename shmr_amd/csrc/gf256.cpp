@@ -130,7 +130,7 @@ std::vector<uint8_t> Plan::image(bool compact) const {
     std::vector<uint16_t> oi = out_idx;
     if (compact)
         for (unsigned j = 0; j < m; ++j) oi[j] = uint16_t(j);
-    std::memcpy(img.data() + 8 + 2 * size_t(k), oi.data(), 2 * size_t(m));
+    if (m) std::memcpy(img.data() + 8 + 2 * size_t(k), oi.data(), 2 * size_t(m));   // (an empty plan: no null source)
     PermTab* tabs = reinterpret_cast<PermTab*>(img.data() + hdr);
     for (unsigned t = 0; t < k; ++t)
         for (unsigned r = 0; r < m; ++r) tabs[size_t(t) * m + r] = perm_table(rows.at(r, t));
@@ -232,6 +232,59 @@ std::shared_ptr<Plan> Codec::reconstruct_plan(const std::vector<uint8_t>& presen
     plan->m = unsigned(rows.size());
     plan->rows = Matrix(plan->m, k_);
     for (unsigned r = 0; r < plan->m; ++r) std::memcpy(&plan->rows.at(r, 0), rows[r].data(), k_);
+    plans_[key] = plan;
+    return plan;
+}
+
+std::shared_ptr<Plan> Codec::checked_plan(const std::vector<uint8_t>& present, bool data_only, bool no_rebuild) {
+    const unsigned t = k_ + p_;
+    // (two bytes behind the pattern: never a reconstruct_plan key)
+    std::vector<uint8_t> key(t + 2);
+    unsigned np = 0;
+    for (unsigned i = 0; i < t; ++i) np += (key[i] = present[i] ? 1 : 0);
+    key[t] = data_only ? 1 : 0;
+    key[t + 1] = no_rebuild ? 3 : 2;
+    // The stored rows are the reconstruct's own (and its LRU lookup, as in the crate).
+    std::shared_ptr<Plan> rebuilt;
+    if (np != t && !no_rebuild) rebuilt = reconstruct_plan(present, data_only);
+    std::lock_guard<std::mutex> lock(mu_);
+    auto found = plans_.find(key);
+    if (found != plans_.end()) return found->second;
+
+    std::vector<uint16_t> valid, invalid, surplus;
+    for (unsigned i = 0; i < t; ++i) {
+        if (!key[i]) invalid.push_back(uint16_t(i));
+        else if (valid.size() < k_) valid.push_back(uint16_t(i));
+        else surplus.push_back(uint16_t(i));
+    }
+    std::shared_ptr<const Matrix> dec;   // null: every shard present, Dec is the identity
+    if (np != t) dec = data_decode_matrix(valid, invalid);
+
+    auto plan = std::make_shared<Plan>();
+    plan->k = k_;
+    plan->in_idx = valid;
+    const unsigned m_store = rebuilt ? rebuilt->m : 0;
+    plan->n_check = unsigned(surplus.size());
+    plan->m = m_store + plan->n_check;
+    plan->rows = Matrix(plan->m, k_);
+    for (unsigned r = 0; r < m_store; ++r) {
+        plan->out_idx.push_back(rebuilt->out_idx[r]);
+        std::memcpy(&plan->rows.at(r, 0), rebuilt->rows.row(r), k_);
+    }
+    for (unsigned s = 0; s < plan->n_check; ++s) {
+        const uint16_t j = surplus[s];   // >= k: a present data shard is among the first k present
+        plan->out_idx.push_back(j);
+        uint8_t* row = &plan->rows.at(m_store + s, 0);
+        if (!dec) {
+            std::memcpy(row, matrix_.row(j), k_);
+            continue;
+        }
+        for (unsigned d = 0; d < k_; ++d) {
+            const uint8_t f = matrix_.at(j, d);
+            if (!f) continue;
+            for (unsigned c = 0; c < k_; ++c) row[c] ^= mul(f, dec->at(d, c));
+        }
+    }
     plans_[key] = plan;
     return plan;
 }

@@ -73,6 +73,9 @@ struct Plan {
     std::vector<uint16_t> in_idx;   // size k
     std::vector<uint16_t> out_idx;  // size m
     Matrix rows;                    // m x k
+    // Checked plans (Codec::checked_plan): the last n_check rows are compared
+    // with the stored bytes of shard out_idx[m] instead of stored there.
+    unsigned n_check = 0;
     // Device image: [u32 k][u32 m][u16 in_idx[k]][u16 out_idx[m]] padded to
     // 32 B, then PermTab[k][m] (input-major so one shard's rows are contiguous
     // for the kernel).  compact: out_idx[j] = j, i.e. output j goes to slot j
@@ -110,6 +113,16 @@ public:
     // "rebuild data, then re-encode parity" for any input, because Dec
     // maps the sub-shards to the data shards exactly).  Cached per pattern.
     std::shared_ptr<Plan> reconstruct_plan(const std::vector<uint8_t>& present, bool data_only);
+
+    // Checked reconstruct plan for a presence pattern (present.size() == k+p,
+    // at least k present; all present allowed).  Inputs: the first k present
+    // shards, as reconstruct_plan.  Rows: first the rows of
+    // reconstruct_plan(present, data_only), verbatim (none with no_rebuild or
+    // with every shard present); then n_check rows M[k+r] * Dec, one per
+    // surplus shard k+r (the present shards behind the first k: always parity)
+    // in ascending index, Dec = inv(M[inputs]) -- with every shard present Dec
+    // is the identity and they are the encode rows.  Cached per pattern.
+    std::shared_ptr<Plan> checked_plan(const std::vector<uint8_t>& present, bool data_only, bool no_rebuild);
 
     uint64_t decode_cache_hits() const { return hits_; }
     uint64_t decode_cache_misses() const { return misses_; }

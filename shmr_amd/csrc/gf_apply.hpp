@@ -298,6 +298,21 @@ size_t kernel_inventory(KernelInfo* out, size_t cap);
 constexpr int verify_chunks(unsigned rows) { return rows >= 3 ? 2 : 1; }
 hipError_t launch_verify(const ApplyArgs& a, uint32_t* mismatch, unsigned rows, int u, int mode, hipStream_t stream);
 
+// The checked-reconstruct kernels (gf_check.hip;
+// shmr_ec_reconstruct_checked_batch_dev): `a` as for an in-place reconstruct
+// launch of `rows` plan rows from a.row0 (single plan; blocks blk_first + j *
+// blk_stride, or a.blk_list[j]; in_base == out_base, out_bias 0).  Rows
+// [0, nstore) of the group are computed and stored to their out_idx slots (absent
+// shards); rows [nstore, rows) are computed and compared with the bytes at
+// their out_idx slots (present surplus shards, only read): a difference in this
+// launch's tiles ORs bit bits[r] (< 32) into mismatch[blk], blk the block's
+// index as above -- not its position in the launch.  Writes no word of a
+// block without a difference.  mode 0: full 4 KiB tiles; mode 1: one partial
+// tail tile per block; mode 2: byte-granular, any alignment.  One workgroup per
+// tile.  Not part of kernel_inventory.
+hipError_t launch_check(const ApplyArgs& a, uint32_t* mismatch, unsigned rows, unsigned nstore, const uint32_t* bits,
+                        int mode, hipStream_t stream);
+
 // The single-shard location kernels (gf_locate.hip; shmr_ec_locate_batch_dev),
 // behind a launch_verify of the same blocks: `a` as for launch_verify of the
 // first row group (a.row0 = 0, rows = min(p, 4) in [2, 4]); mismatch[j] the

@@ -492,6 +492,74 @@ class ReedSolomon:
         _check(self._L.shmr_ec_reconstruct_batch_dev(self._h, ctypes.c_void_p(shards.data_ptr()), shards.stride(1),
                                                    shards.stride(0), _ptr(pr), B, L, int(data_only), dev, stream))
 
+    CHECK_DATA_ONLY, CHECK_NO_REBUILD = 1, 2   # SHMR_EC_CHECK_* (include/shmr_ec.h)
+
+    def reconstruct_checked_batch_dev(self, shards, present: np.ndarray, shard_len: Optional[int] = None,
+                                      data_only: bool = False, rebuild: bool = True, device: Optional[int] = None,
+                                      out=None):
+        """``reconstruct_batch_dev`` that also compares the surplus shards -- the
+        present shards behind the first k, which a plain reconstruct never
+        reads -- with what the inputs say they should hold, in the same pass
+        (``shmr_ec_reconstruct_checked_batch_dev``).  shards, present,
+        shard_len, data_only as ``reconstruct_batch_dev``; ``rebuild=False``
+        compares only and writes no shard ("verify with erasures").
+
+        Returns a ``torch.int32`` tensor ``[B]`` on the tensors' device, as
+        ``verify_batch_dev`` does (``out``: a tensor to overwrite instead): 0 =
+        every surplus shard of block b agrees, else bit min(r, 31) for every
+        surplus parity row r that differs.  Rebuilt bytes are written either
+        way; a non-zero word says they are suspect.  Enqueued on torch's
+        current stream; not capturable into a graph."""
+        import torch
+        if shards.dim() != 3:
+            raise TypeError("shards must be a [blocks, total, bytes] tensor")
+        B, t = shards.shape[0], self.total_shard_count()
+        L = shard_len if shard_len is not None else shards.stride(1)
+        self._check_batch_tensor(shards, t, shards.stride(1), L)
+        pr = np.ascontiguousarray(present, dtype=np.uint8)
+        if pr.size != B * t:
+            raise ValueError(f"present must hold {B} x {t} flags")
+        pr = pr.reshape(B, t)
+        self._check_addressable(shards)
+        if not shards.is_cuda:
+            raise TypeError("reconstruct_checked_batch_dev takes a tensor on the GPU")
+        if out is None:
+            out = torch.empty(B, dtype=torch.int32, device=shards.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.device != shards.device
+              or out.dim() != 1 or out.shape[0] != B or not out.is_contiguous()):
+            raise TypeError(f"out must be a contiguous torch.int32 [{B}] tensor on {shards.device}")
+        dev, stream = self._stream_and_device(shards)
+        dev = dev if device is None else int(device)
+        flags = (self.CHECK_DATA_ONLY if data_only else 0) | (0 if rebuild else self.CHECK_NO_REBUILD)
+        _check(self._L.shmr_ec_reconstruct_checked_batch_dev(
+            self._h, ctypes.c_void_p(shards.data_ptr()), shards.stride(1), shards.stride(0), _ptr(pr), B, L, flags,
+            ctypes.c_void_p(out.data_ptr()), dev, stream))
+        return out
+
+    def checked_rows(self, present: Sequence[bool]) -> int:
+        """The word a damaged input gives: bit min(r, 31) for every parity row r
+        that ``reconstruct_checked_batch_dev`` compares under this pattern."""
+        pr = np.array([1 if x else 0 for x in present], dtype=np.uint8)
+        rows = ctypes.c_uint32()
+        _check(self._L.shmr_ec_checked_rows(self._h, _ptr(pr), len(pr), ctypes.byref(rows)))
+        return int(rows.value)
+
+    def checked_plan(self, present: Sequence[bool], data_only: bool = False, rebuild: bool = True):
+        """(in_idx, out_idx, rows, n_store) of the plan the checked reconstruct
+        runs for this pattern: rows[:n_store] are stored to their out_idx
+        (``reconstruct_plan``'s rows), rows[n_store:] compared with theirs."""
+        t, k = self.total_shard_count(), self.data_shard_count()
+        pr = np.array([1 if x else 0 for x in present], dtype=np.uint8)
+        in_idx = (ctypes.c_uint16 * k)()
+        out_idx = (ctypes.c_uint16 * t)()
+        rows = np.zeros(t * k, dtype=np.uint8)
+        ns, nc = ctypes.c_uint32(), ctypes.c_uint32()
+        flags = (self.CHECK_DATA_ONLY if data_only else 0) | (0 if rebuild else self.CHECK_NO_REBUILD)
+        _check(self._L.shmr_ec_checked_plan(self._h, _ptr(pr), len(pr), flags, in_idx, out_idx, _ptr(rows), rows.size,
+                                            ctypes.byref(ns), ctypes.byref(nc)))
+        m = ns.value + nc.value
+        return list(in_idx), list(out_idx)[:m], rows[:m * k].reshape(m, k).copy(), int(ns.value)
+
     def reconstruct_batch_dev_out(self, shards, present: np.ndarray, out, shard_len: Optional[int] = None,
                                   data_only: bool = False, device: Optional[int] = None) -> None:
         """Rebuild the absent shards of every block into a separate compact
