@@ -66,13 +66,16 @@ def _patterns(k, p, arrangement):
 
 
 class Case:
-    def __init__(self, k, p, L, gpu, arrangement="plain", odd=False):
+    def __init__(self, k, p, L, gpu, arrangement="plain", odd=False, present=None):
+        """present: a [blocks, k + p] array of the batch's own patterns (any
+        block count) in place of an arrangement's six."""
         import torch
         self.k, self.p, self.t, self.L = k, p, k + p, L
         t = k + p
+        self.present = _patterns(k, p, arrangement) if present is None else np.array(present, np.uint8)
+        self.B = B = len(self.present)
         self.pitch = pitch = (L // 64 + 1) * 64 + (1 if odd else 0)     # above len
         self.off = off = GUARD + (1 if odd else 0)
-        self.present = _patterns(k, p, arrangement)
         rng = np.random.default_rng([k, p, L, int(odd)])
         img = np.full(off + B * t * pitch + GUARD, SENT, np.uint8)
         cw = img[off:off + B * t * pitch].reshape(B, t, pitch)
@@ -93,11 +96,11 @@ class Case:
         self.words = torch.full((B + 2,), WORD_SENT, dtype=torch.int32, device=gpu)
 
     def view(self, img):
-        return img[self.off:self.off + B * self.t * self.pitch].reshape(B, self.t, self.pitch)
+        return img[self.off:self.off + self.B * self.t * self.pitch].reshape(self.B, self.t, self.pitch)
 
     def dev_view(self, buf):
         import torch
-        return torch.as_strided(buf, (B, self.t, self.pitch), (self.t * self.pitch, self.pitch, 1), self.off)
+        return torch.as_strided(buf, (self.B, self.t, self.pitch), (self.t * self.pitch, self.pitch, 1), self.off)
 
     def reset(self):
         self.buf.copy_(self.start_dev)
@@ -107,12 +110,12 @@ class Case:
         import torch
         self.words.fill_(WORD_SENT)
         out = self.rs.reconstruct_checked_batch_dev(self.shards, self.present, shard_len=self.L, data_only=data_only,
-                                                    rebuild=rebuild, out=self.words[1:B + 1])
-        assert out.dtype == torch.int32 and out.shape == (B,) and out.data_ptr() == self.words[1:].data_ptr()
+                                                    rebuild=rebuild, out=self.words[1:self.B + 1])
+        assert out.dtype == torch.int32 and out.shape == (self.B,) and out.data_ptr() == self.words[1:].data_ptr()
         torch.cuda.synchronize()
         w = self.words.cpu().numpy().view(np.uint32)
-        assert w[0] == WORD_SENT and w[B + 1] == WORD_SENT, "a word next to d_mismatch was written"
-        return w[1:B + 1].copy()
+        assert w[0] == WORD_SENT and w[self.B + 1] == WORD_SENT, "a word next to d_mismatch was written"
+        return w[1:self.B + 1].copy()
 
     def flip(self, flips, x=0x41):
         for b, s, col in flips:
@@ -129,7 +132,7 @@ class Case:
             v[b, s, col] ^= x
         if not rebuilt:
             return img
-        for b in range(B):
+        for b in range(self.B):
             pr = self.present[b]
             if pr.all():
                 continue

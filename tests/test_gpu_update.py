@@ -43,10 +43,12 @@ def _encode(k, p, d):
 
 
 class Case:
-    """Codewords of one (k, p, L) in the guarded two-region device layout."""
+    """Codewords of one (k, p, L) in the guarded two-region device layout
+    (blocks: the batch's block count, B unless given)."""
 
-    def __init__(self, k, p, L, gpu, seed, shift=0):
+    def __init__(self, k, p, L, gpu, seed, shift=0, blocks=B):
         import torch
+        self.B = B = blocks
         self.k, self.p, self.L, self.pitch, self.gpu = k, p, L, _pitch(L), gpu
         rng = np.random.default_rng(seed)
         self.rng = rng
@@ -69,8 +71,8 @@ class Case:
 
     def views(self, img):
         k, p, pitch = self.k, self.p, self.pitch
-        return (img[self.data_off:self.data_off + B * k * pitch].reshape(B, k, pitch),
-                img[self.par_off:self.par_off + B * p * pitch].reshape(B, p, pitch))
+        return (img[self.data_off:self.data_off + self.B * k * pitch].reshape(self.B, k, pitch),
+                img[self.par_off:self.par_off + self.B * p * pitch].reshape(self.B, p, pitch))
 
     def reset(self, img=None):
         import torch
