@@ -599,6 +599,17 @@ int host_block(shmr_ec_t* rs, core::OpClass op, bool data_only, uint8_t* const* 
 
 int arg_ok(bool ok) { return ok ? SHMR_EC_OK : SHMR_EC_INVALID_ARGUMENT; }
 
+// Result words (uint32_t / int32_t arrays in device memory): given, and 4-byte aligned.
+bool words_given(const void* p) { return p && uintptr_t(p) % alignof(uint32_t) == 0; }
+
+// The data / parity pitch layout of the *_batch_dev calls.  The layout's
+// output side is the parity, also where a call only reads it (verify, locate).
+core::Layout batch_layout(const Codec& c, const uint8_t* d_data, size_t data_shard_pitch, size_t data_block_pitch,
+                          const uint8_t* d_parity, size_t parity_shard_pitch, size_t parity_block_pitch) {
+    return core::Layout{d_data,           const_cast<uint8_t*>(d_parity), data_block_pitch, data_shard_pitch,
+                        parity_block_pitch, parity_shard_pitch,             c.k()};
+}
+
 // A batch call on device memory, after its checks of rs and the presence flags:
 // an empty batch is done, empty shards are refused, then `check` (the call's own
 // pointers and flags, before any device is asked for), then `launch` with the
@@ -844,8 +855,8 @@ int shmr_ec_encode_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_s
         if (!rs) return SHMR_EC_INVALID_ARGUMENT;
         return batch_dev(nblocks, shard_len, device, [&] { return arg_ok(d_data && d_parity); }, [&] {
             Codec& c = *rs->codec;
-            const core::Layout L{d_data, d_parity, data_block_pitch, data_shard_pitch, parity_block_pitch,
-                                 parity_shard_pitch, c.k()};
+            const core::Layout L = batch_layout(c, d_data, data_shard_pitch, data_block_pitch, d_parity,
+                                                parity_shard_pitch, parity_block_pitch);
             return core::encode_on_device(c, device, L, nblocks, shard_len, static_cast<hipStream_t>(stream));
         });
     });
@@ -856,12 +867,11 @@ int shmr_ec_verify_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_s
                              size_t nblocks, size_t shard_len, uint32_t* d_mismatch, int device, void* stream) {
     return guarded([&]() -> int {
         if (!rs) return SHMR_EC_INVALID_ARGUMENT;
-        const bool given = d_data && d_parity && d_mismatch && uintptr_t(d_mismatch) % alignof(uint32_t) == 0;
+        const bool given = d_data && d_parity && words_given(d_mismatch);
         return batch_dev(nblocks, shard_len, device, [&] { return arg_ok(given); }, [&] {
             Codec& c = *rs->codec;
-            // (the layout's output side is the stored parity: the verify kernels only read it)
-            const core::Layout L{d_data, const_cast<uint8_t*>(d_parity), data_block_pitch, data_shard_pitch,
-                                 parity_block_pitch, parity_shard_pitch, c.k()};
+            const core::Layout L = batch_layout(c, d_data, data_shard_pitch, data_block_pitch, d_parity,
+                                                parity_shard_pitch, parity_block_pitch);
             return core::verify_on_device(c, device, L, nblocks, shard_len, d_mismatch, static_cast<hipStream_t>(stream));
         });
     });
@@ -879,12 +889,11 @@ int shmr_ec_locate_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_s
     return guarded([&]() -> int {
         if (!rs || !rs->codec->locate_plan()) return SHMR_EC_INVALID_ARGUMENT;
         Codec& c = *rs->codec;
-        const bool given = d_data && d_parity && d_mismatch && d_located && d_work &&
-                           (uintptr_t(d_mismatch) | uintptr_t(d_located) | uintptr_t(d_work)) % alignof(uint32_t) == 0 &&
-                           work_bytes >= core::locate_work_bytes(c, nblocks);
+        const bool given = d_data && d_parity && words_given(d_mismatch) && words_given(d_located) &&
+                           words_given(d_work) && work_bytes >= core::locate_work_bytes(c, nblocks);
         return batch_dev(nblocks, shard_len, device, [&] { return arg_ok(given); }, [&] {
-            const core::Layout L{d_data, const_cast<uint8_t*>(d_parity), data_block_pitch, data_shard_pitch,
-                                 parity_block_pitch, parity_shard_pitch, c.k()};
+            const core::Layout L = batch_layout(c, d_data, data_shard_pitch, data_block_pitch, d_parity,
+                                                parity_shard_pitch, parity_block_pitch);
             return core::locate_on_device(c, device, L, nblocks, shard_len, d_mismatch, d_located,
                                           static_cast<uint32_t*>(d_work), static_cast<hipStream_t>(stream));
         });
@@ -901,14 +910,12 @@ int shmr_ec_scrub_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pi
         Codec& c = *rs->codec;
         hipStream_t stream = static_cast<hipStream_t>(stream_);
         return batch_dev(nblocks, shard_len, device, [&] { return arg_ok(d_data && d_parity); }, [&]() -> int {
-            bool capturing = false;
-            int rc = core::device_init(device, stream);
-            if (rc || (rc = core::capture_state(stream, &capturing))) return rc;
-            if (capturing) return SHMR_EC_INVALID_ARGUMENT;   // it waits for its own results
+            int rc = core::refuse_capture(device, stream);   // it waits for its own results
+            if (rc) return rc;
             counts[0] = counts[1] = counts[2] = 0;
             const unsigned k = c.k(), t = k + c.p();
-            const core::Layout L{d_data, d_parity, data_block_pitch, data_shard_pitch, parity_block_pitch,
-                                 parity_shard_pitch, k};
+            const core::Layout L = batch_layout(c, d_data, data_shard_pitch, data_block_pitch, d_parity,
+                                                parity_shard_pitch, parity_block_pitch);
             // pooled scratch (grown without a free): the words, the answers, the candidate bitmaps
             const size_t words_bytes = size_t(core::round_up(nblocks * sizeof(uint32_t), 256));
             core::StagingLease lease;
@@ -980,8 +987,8 @@ int shmr_ec_update_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_p
                           shmr::update::plan(updates, nupdates, nblocks, c.k(), shard_len, src_bytes, &up));
         };
         return batch_dev(nblocks, shard_len, device, check, [&] {
-            const core::Layout L{d_data, d_parity, data_block_pitch, data_shard_pitch, parity_block_pitch,
-                                 parity_shard_pitch, c.k()};
+            const core::Layout L = batch_layout(c, d_data, data_shard_pitch, data_block_pitch, d_parity,
+                                                parity_shard_pitch, parity_block_pitch);
             return core::update_on_device(c, device, L, up, d_src, static_cast<hipStream_t>(stream));
         });
     });
@@ -1026,8 +1033,7 @@ int shmr_ec_reconstruct_checked_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size
         if (!rs) return SHMR_EC_INVALID_ARGUMENT;
         Codec& c = *rs->codec;
         const int known = SHMR_EC_CHECK_DATA_ONLY | SHMR_EC_CHECK_NO_REBUILD;
-        const bool given = d_shards && present && d_mismatch && uintptr_t(d_mismatch) % alignof(uint32_t) == 0 &&
-                           (flags & ~known) == 0;
+        const bool given = d_shards && present && words_given(d_mismatch) && (flags & ~known) == 0;
         // (no launch on a bad batch)
         auto check = [&] { return given ? core::validate_presence(c, present, nblocks) : arg_ok(false); };
         return batch_dev(nblocks, shard_len, device, check, [&] {

@@ -906,7 +906,101 @@ int launch_split(kern::ApplyArgs& a, uint64_t len, uint64_t tb, int full_mode, i
     }
     return SHMR_EC_OK;
 }
+
+// The row groups [0, nrows) of a compare launch set (parity check, location,
+// checked reconstruct) over the blocks `a` names: per group of <= 4 rows one
+// full-tile launch plus, when len is not a multiple of the tile, one over the
+// partial last tile -- launch_split, as an encode's launch_set without its
+// fused-tail and segment forms.  Misaligned shards take the same kernels where
+// the device serves unaligned vector access, else the byte-granular one in
+// 4 KiB tiles.  chunks(rows): the full tiles' 16-byte chunks per lane;
+// launch(rows, row0, mode, u) enqueues `a` in tiles of u chunks (a hipError_t).
+template <class Chunks, class Launch>
+int compare_groups(int dev, const Layout& L, kern::ApplyArgs& a, uint32_t nrows, uint64_t len, Chunks chunks,
+                   Launch launch) {
+    const bool aligned = layout_aligned16(L) || unaligned_vector(dev);
+    for (uint32_t row0 = 0; row0 < nrows; row0 += kern::kMaxRowsPerLaunch) {
+        const uint32_t rows = std::min<uint32_t>(kern::kMaxRowsPerLaunch, nrows - row0);
+        count_device(dev, kDevLaunches);
+        a.row0 = row0;
+        const int u = aligned ? chunks(rows) : 1;
+        const int rc = launch_split(a, len, kern::tile_bytes(u), aligned ? 0 : -1, aligned ? 1 : 2, [&](int mode) -> int {
+            SHMR_HIP_TRY(launch(rows, row0, mode, mode == 0 ? u : 1));
+            return SHMR_EC_OK;
+        });
+        if (rc) return rc;
+    }
+    return SHMR_EC_OK;
+}
+
+// 4 KiB full tiles at every row count (location, checked reconstruct).
+int tile_4k(unsigned) { return 1; }
+
+// apply_args over the batch's own block sequence 0, 1, ... nblocks-1 (encode plans).
+kern::ApplyArgs batch_args(const Layout& L, const Plan& plan, const uint8_t* dplan, uint64_t len, uint64_t nblocks) {
+    kern::ApplyArgs a = apply_args(L, plan, dplan, len);
+    a.blk_first = 0;
+    a.blk_stride = 1;
+    a.nblk = nblocks;
+    a.in_identity = 1;
+    return a;
+}
+
+// The blocks of a batch by presence pattern; block b is named slots[b] where
+// slots are given.  Complete blocks are left out unless keep_complete (a
+// reconstruct has nothing to do for them, a checked reconstruct compares them).
+using PatternGroups = std::map<std::vector<uint8_t>, std::vector<uint64_t>>;
+int group_patterns(const Codec& c, const uint8_t* present, uint64_t nblocks, const uint64_t* slots, bool keep_complete,
+                   PatternGroups* groups) {
+    const unsigned k = c.k(), t = k + c.p();
+    for (uint64_t b = 0; b < nblocks; ++b) {
+        const uint8_t* pr = present + b * t;
+        std::vector<uint8_t> key(t);
+        unsigned np = 0;
+        for (unsigned i = 0; i < t; ++i) np += (key[i] = pr[i] ? 1 : 0);
+        if (np == t && !keep_complete) continue;        // crate: all present -> Ok(())
+        if (np < k) return SHMR_EC_TOO_FEW_SHARDS_PRESENT;
+        (*groups)[std::move(key)].push_back(slots ? slots[b] : b);
+    }
+    return SHMR_EC_OK;
+}
+
+// Whether blocks[0 .. n) is an arithmetic sequence (*stride: its step; 1 for n <= 1).
+template <class T>
+bool arith_stride(const T* blocks, size_t n, uint64_t* stride) {
+    *stride = n > 1 ? uint64_t(blocks[1]) - blocks[0] : 1;
+    for (size_t i = 1; i < n; ++i)
+        if (uint64_t(blocks[i]) - blocks[i - 1] != *stride) return false;
+    return true;
+}
+
+// The blocks [0, n) as uploaded 32-bit block lists, a ring slot per chunk:
+// launch(d_list, cnt) enqueues each chunk's launches.
+template <class Launch>
+int with_block_lists(int dev, hipStream_t stream, const uint64_t* blocks, uint64_t n, Launch launch) {
+    const uint64_t per = UploadRing::kSlotBytes / sizeof(uint32_t);
+    for (uint64_t c0 = 0; c0 < n; c0 += per) {
+        const uint64_t cnt = std::min(per, n - c0);
+        const int rc = with_table(
+            dev, stream, size_t(cnt) * sizeof(uint32_t),
+            [&](uint8_t* h) {
+                uint32_t* l = reinterpret_cast<uint32_t*>(h);
+                for (uint64_t j = 0; j < cnt; ++j) l[j] = uint32_t(blocks[c0 + j]);
+            },
+            [&](const uint8_t* d) { return launch(reinterpret_cast<const uint32_t*>(d), cnt); });
+        if (rc) return rc;
+    }
+    return SHMR_EC_OK;
+}
 }  // namespace
+
+int refuse_capture(int dev, hipStream_t stream) {
+    int rc = device_init(dev, stream);
+    if (rc) return rc;
+    bool capturing = false;
+    if ((rc = capture_state(stream, &capturing))) return rc;
+    return capturing ? SHMR_EC_INVALID_ARGUMENT : SHMR_EC_OK;
+}
 
 int launch_set(Plan& plan, int dev, const Layout& L, const BlockSet& bs, uint64_t len, hipStream_t stream,
                OpClass op) {
@@ -1044,25 +1138,12 @@ int launch_slots(Plan& plan, int dev, const Layout& L, const uint64_t* slots, ui
         if (rc) return rc;
         return launch_runs(plan, dev, L, runs, n, len, stream, op, [&](const grid::Run&, int*) { return dp; });
     }
-    // an uploaded block list, a ring slot per chunk
-    const uint64_t per = UploadRing::kSlotBytes / sizeof(uint32_t);
-    for (uint64_t c0 = 0; c0 < n; c0 += per) {
-        const uint64_t cnt = std::min(per, n - c0);
-        const int rc = with_table(
-            dev, stream, size_t(cnt) * sizeof(uint32_t),
-            [&](uint8_t* h) {
-                uint32_t* l = reinterpret_cast<uint32_t*>(h);
-                for (uint64_t j = 0; j < cnt; ++j) l[j] = uint32_t(slots[c0 + j]);
-            },
-            [&](const uint8_t* d) {
-                BlockSet bs;
-                bs.n = cnt;
-                bs.d_list = reinterpret_cast<const uint32_t*>(d);
-                return launch_set(plan, dev, L, bs, len, stream, op);
-            });
-        if (rc) return rc;
-    }
-    return SHMR_EC_OK;
+    return with_block_lists(dev, stream, slots, n, [&](const uint32_t* d_list, uint64_t cnt) {
+        BlockSet bs;
+        bs.n = cnt;
+        bs.d_list = d_list;
+        return launch_set(plan, dev, L, bs, len, stream, op);
+    });
 }
 
 int encode_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint64_t len, hipStream_t stream,
@@ -1080,11 +1161,8 @@ int encode_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
 
 // ===========================================================================
 // Parity check (ReedSolomon::verify).  The encode plan over the encode layout,
-// L.out_base being the stored parity: per group of <= 4 parity rows one
-// full-tile launch plus, when len is not a multiple of the tile, one launch
-// over the partial last tile -- launch_split, as an encode's launch_set, without
-// its fused-tail and segment forms.  Misaligned shards take the same kernels
-// where the device serves unaligned vector access, else the byte-granular one.
+// L.out_base being the stored parity: the row groups of compare_groups, the
+// full tiles in the measured tile size (verify_chunks).
 // ===========================================================================
 int verify_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint64_t len, uint32_t* d_mismatch,
                      hipStream_t stream) {
@@ -1098,24 +1176,10 @@ int verify_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
     rc = plan_on_device(plan, dev, stream, false, &dplan);
     if (rc) return rc;
     count_device(dev, kDevBlocksVerified, nblocks);
-    const bool aligned = layout_aligned16(L) || unaligned_vector(dev);
-    kern::ApplyArgs a = apply_args(L, plan, dplan, len);
-    a.blk_first = 0;
-    a.blk_stride = 1;
-    a.nblk = nblocks;
-    a.in_identity = 1;
-    for (uint32_t row0 = 0; row0 < plan.m; row0 += kern::kMaxRowsPerLaunch) {
-        const uint32_t rows = std::min<uint32_t>(kern::kMaxRowsPerLaunch, plan.m - row0);
-        count_device(dev, kDevLaunches);
-        a.row0 = row0;
-        const int u = aligned ? verify_chunks(rows) : 1;   // the byte-granular kernel (mode 2): 4 KiB tiles
-        rc = launch_split(a, len, kern::tile_bytes(u), aligned ? 0 : -1, aligned ? 1 : 2, [&](int mode) -> int {
-            SHMR_HIP_TRY(kern::launch_verify(a, d_mismatch, rows, mode == 0 ? u : 1, mode, stream));
-            return SHMR_EC_OK;
-        });
-        if (rc) return rc;
-    }
-    return SHMR_EC_OK;
+    kern::ApplyArgs a = batch_args(L, plan, dplan, len, nblocks);
+    return compare_groups(dev, L, a, plan.m, len, verify_chunks, [&](uint32_t rows, uint32_t, int mode, int u) {
+        return kern::launch_verify(a, d_mismatch, rows, u, mode, stream);
+    });
 }
 
 // ===========================================================================
@@ -1133,33 +1197,21 @@ int locate_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
     const std::shared_ptr<Plan> lplan = c.locate_plan();
     if (!lplan) return SHMR_EC_INVALID_ARGUMENT;
     // Not inside a graph capture (shmr_ec.h): refused before anything is enqueued.
-    int rc = device_init(dev, stream);
+    int rc = refuse_capture(dev, stream);
     if (rc) return rc;
-    bool capturing = false;
-    if ((rc = capture_state(stream, &capturing))) return rc;
-    if (capturing) return SHMR_EC_INVALID_ARGUMENT;
     rc = verify_on_device(c, dev, L, nblocks, len, d_mismatch, stream);
     if (rc || nblocks == 0) return rc;
     Plan& plan = *c.encode_plan();
-    const unsigned rows = locate::rows_used(plan.m);
     SHMR_HIP_TRY(kern::launch_locate_preset(d_cand, nblocks, plan.k, stream));
     const uint8_t *dplan = nullptr, *dratio = nullptr;
     rc = plan_on_device(plan, dev, stream, false, &dplan);
     if (rc) return rc;
     rc = plan_on_device(*lplan, dev, stream, false, &dratio);
     if (rc) return rc;
-    const bool aligned = layout_aligned16(L) || unaligned_vector(dev);
-    kern::ApplyArgs a = apply_args(L, plan, dplan, len);
-    a.blk_first = 0;
-    a.blk_stride = 1;
-    a.nblk = nblocks;
-    a.in_identity = 1;
-    a.row0 = 0;
-    count_device(dev, kDevLaunches);
-    rc = launch_split(a, len, kern::tile_bytes(1), aligned ? 0 : -1, aligned ? 1 : 2, [&](int mode) -> int {
-        SHMR_HIP_TRY(kern::launch_locate(a, dratio + plan_tab_off(lplan->k, lplan->m), d_mismatch, d_cand, rows, plan.m,
-                                         mode, stream));
-        return SHMR_EC_OK;
+    kern::ApplyArgs a = batch_args(L, plan, dplan, len, nblocks);
+    rc = compare_groups(dev, L, a, locate::rows_used(plan.m), len, tile_4k, [&](uint32_t rows, uint32_t, int mode, int) {
+        return kern::launch_locate(a, dratio + plan_tab_off(lplan->k, lplan->m), d_mismatch, d_cand, rows, plan.m, mode,
+                                   stream);
     });
     if (rc) return rc;
     SHMR_HIP_TRY(kern::launch_locate_resolve(d_mismatch, d_cand, d_located, nblocks, plan.k, plan.m, stream));
@@ -1176,11 +1228,8 @@ int locate_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
 int update_on_device(Codec& c, int dev, const Layout& L, const update::Plan& up, const uint8_t* d_src,
                      hipStream_t stream) {
     static_assert(kUpdateTablePieces * sizeof(update::DevPiece) == UploadRing::kSlotBytes, "one ring slot per chunk");
-    int rc = device_init(dev, stream);
+    int rc = refuse_capture(dev, stream);
     if (rc) return rc;
-    bool capturing = false;
-    if ((rc = capture_state(stream, &capturing))) return rc;
-    if (capturing) return SHMR_EC_INVALID_ARGUMENT;
     Plan& plan = *c.encode_plan();
     const uint8_t* dplan = nullptr;
     rc = plan_on_device(plan, dev, stream, false, &dplan);
@@ -1262,20 +1311,10 @@ int reconstruct_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_p
 
 int reconstruct_on_device(Codec& c, int dev, const Layout& L, const uint8_t* present, uint64_t nblocks, uint64_t len,
                           bool data_only, hipStream_t stream, const uint64_t* slots) {
-    const unsigned k = c.k(), t = k + c.p();
     int rc = device_init(dev, stream);
     if (rc) return rc;
-    std::map<std::vector<uint8_t>, std::vector<uint64_t>> groups;   // pattern -> blocks
-    for (uint64_t b = 0; b < nblocks; ++b) {
-        const uint8_t* pr = present + b * t;
-        unsigned np = 0;
-        for (unsigned i = 0; i < t; ++i) np += pr[i] ? 1 : 0;
-        if (np == t) continue;                          // crate: all present -> Ok(())
-        if (np < k) return SHMR_EC_TOO_FEW_SHARDS_PRESENT;
-        std::vector<uint8_t> key(t);
-        for (unsigned i = 0; i < t; ++i) key[i] = pr[i] ? 1 : 0;
-        groups[key].push_back(slots ? slots[b] : b);
-    }
+    PatternGroups groups;
+    if ((rc = group_patterns(c, present, nblocks, slots, false, &groups))) return rc;
     if (groups.empty()) return SHMR_EC_OK;
     for (auto& g : groups) count_device(dev, kDevBlocksReconstructed, g.second.size());
     // Patterns with the same number of rebuilt shards share one multi-plan
@@ -1301,11 +1340,8 @@ int reconstruct_on_device(Codec& c, int dev, const Layout& L, const uint8_t* pre
     for (auto& kv : by_m) {
         Group& grp = kv.second;
         // A single pattern over an arithmetic block sequence needs no upload.
-        bool arith = grp.plans.size() == 1;
-        const uint64_t stride = grp.blocks.size() > 1 ? uint64_t(grp.blocks[1]) - grp.blocks[0] : 1;
-        for (size_t i = 1; arith && i < grp.blocks.size(); ++i)
-            arith = uint64_t(grp.blocks[i]) - grp.blocks[i - 1] == stride;
-        if (arith) {
+        uint64_t stride = 1;
+        if (grp.plans.size() == 1 && arith_stride(grp.blocks.data(), grp.blocks.size(), &stride)) {
             BlockSet bs;
             bs.first = grp.blocks[0];
             bs.stride = stride;
@@ -1391,38 +1427,26 @@ int reconstruct_on_device(Codec& c, int dev, const Layout& L, const uint8_t* pre
 // ===========================================================================
 // Checked reconstruct.  Blocks are grouped by presence pattern as above; every
 // pattern is a single-plan launch set of its checked plan (stored rows, then
-// compare rows), split per row group as a verify's launches (launch_split, 4 KiB
-// tiles).  The store / compare boundary of a group is nstore = the stored rows
-// that fall into it; a compare row's bit is its parity row index.
+// compare rows) in the row groups of compare_groups (4 KiB tiles).  The store /
+// compare boundary of a group is nstore = the stored rows that fall into it; a
+// compare row's bit is its parity row index.
 // ===========================================================================
 int checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch, uint64_t block_pitch,
                       const uint8_t* present, uint64_t nblocks, uint64_t len, bool data_only, bool no_rebuild,
                       uint32_t* d_mismatch, hipStream_t stream) {
     const unsigned k = c.k(), t = k + c.p();
-    int rc = device_init(dev, stream);
-    if (rc) return rc;
     // Not inside a graph capture (shmr_ec.h): refused before anything is enqueued.
-    bool capturing = false;
-    if ((rc = capture_state(stream, &capturing))) return rc;
-    if (capturing) return SHMR_EC_INVALID_ARGUMENT;
+    int rc = refuse_capture(dev, stream);
+    if (rc) return rc;
     if (nblocks == 0) return SHMR_EC_OK;
     if (nblocks > 0xffffffffull) return SHMR_EC_INVALID_ARGUMENT;   // block lists are 32-bit
-    std::map<std::vector<uint8_t>, std::vector<uint32_t>> groups;   // pattern -> blocks
-    uint64_t degraded = 0;
-    for (uint64_t b = 0; b < nblocks; ++b) {
-        const uint8_t* pr = present + b * t;
-        std::vector<uint8_t> key(t);
-        unsigned np = 0;
-        for (unsigned i = 0; i < t; ++i) np += (key[i] = pr[i] ? 1 : 0);
-        if (np < k) return SHMR_EC_TOO_FEW_SHARDS_PRESENT;
-        degraded += np != t ? 1 : 0;
-        groups[key].push_back(uint32_t(b));
-    }
+    PatternGroups groups;
+    if ((rc = group_patterns(c, present, nblocks, nullptr, true, &groups))) return rc;
+    const auto complete = groups.find(std::vector<uint8_t>(t, 1));
     SHMR_HIP_TRY(hipMemsetAsync(d_mismatch, 0, size_t(nblocks) * sizeof(uint32_t), stream));
     count_device(dev, kDevBlocksVerified, nblocks);
-    count_device(dev, kDevBlocksReconstructed, degraded);
+    count_device(dev, kDevBlocksReconstructed, nblocks - (complete == groups.end() ? 0 : complete->second.size()));
     const Layout L{d_shards, d_shards, block_pitch, shard_pitch, block_pitch, shard_pitch, 0};
-    const bool aligned = layout_aligned16(L) || unaligned_vector(dev);
     for (auto& g : groups) {
         const std::shared_ptr<Plan> planp = c.checked_plan(g.first, data_only, no_rebuild);
         Plan& plan = *planp;
@@ -1433,49 +1457,28 @@ int checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch
         const uint32_t m_store = plan.m - plan.n_check;
         kern::ApplyArgs a = apply_args(L, plan, dplan, len);
         // the row groups of the pattern over the blocks `a` names
-        auto launch_groups = [&]() -> int {
-            for (uint32_t row0 = 0; row0 < plan.m; row0 += kern::kMaxRowsPerLaunch) {
-                const uint32_t rows = std::min<uint32_t>(kern::kMaxRowsPerLaunch, plan.m - row0);
-                const uint32_t nstore = m_store > row0 ? std::min(m_store - row0, rows) : 0;
-                uint32_t bits[kern::kMaxRowsPerLaunch] = {};
-                for (uint32_t r = nstore; r < rows; ++r) bits[r] = std::min<uint32_t>(plan.out_idx[row0 + r] - k, 31);
-                count_device(dev, kDevLaunches);
-                a.row0 = row0;
-                const int lrc = launch_split(a, len, kern::tile_bytes(1), aligned ? 0 : -1, aligned ? 1 : 2,
-                                             [&](int mode) -> int {
-                                                 SHMR_HIP_TRY(kern::launch_check(a, d_mismatch, rows, nstore, bits, mode,
-                                                                                 stream));
-                                                 return SHMR_EC_OK;
-                                             });
-                if (lrc) return lrc;
-            }
-            return SHMR_EC_OK;
+        auto launch = [&](uint32_t rows, uint32_t row0, int mode, int) {
+            const uint32_t nstore = m_store > row0 ? std::min(m_store - row0, rows) : 0;
+            uint32_t bits[kern::kMaxRowsPerLaunch] = {};
+            for (uint32_t r = nstore; r < rows; ++r) bits[r] = std::min<uint32_t>(plan.out_idx[row0 + r] - k, 31);
+            return kern::launch_check(a, d_mismatch, rows, nstore, bits, mode, stream);
         };
-        const std::vector<uint32_t>& blocks = g.second;
-        bool arith = true;
-        const uint64_t stride = blocks.size() > 1 ? uint64_t(blocks[1]) - blocks[0] : 1;
-        for (size_t i = 1; arith && i < blocks.size(); ++i) arith = uint64_t(blocks[i]) - blocks[i - 1] == stride;
-        if (arith) {
+        auto launch_groups = [&]() { return compare_groups(dev, L, a, plan.m, len, tile_4k, launch); };
+        const std::vector<uint64_t>& blocks = g.second;
+        uint64_t stride = 1;
+        if (arith_stride(blocks.data(), blocks.size(), &stride)) {
             a.blk_first = blocks[0];
             a.blk_stride = stride;
             a.nblk = blocks.size();
-            if ((rc = launch_groups())) return rc;
-            continue;
+            rc = launch_groups();
+        } else {
+            rc = with_block_lists(dev, stream, blocks.data(), blocks.size(), [&](const uint32_t* d_list, uint64_t cnt) {
+                a.blk_list = d_list;
+                a.nblk = cnt;
+                return launch_groups();
+            });
         }
-        // an uploaded block list, a ring slot per chunk
-        const size_t per = UploadRing::kSlotBytes / sizeof(uint32_t);
-        for (size_t c0 = 0; c0 < blocks.size(); c0 += per) {
-            const size_t cnt = std::min(per, blocks.size() - c0);
-            rc = with_table(
-                dev, stream, cnt * sizeof(uint32_t),
-                [&](uint8_t* h) { std::memcpy(h, blocks.data() + c0, cnt * sizeof(uint32_t)); },
-                [&](const uint8_t* d) {
-                    a.blk_list = reinterpret_cast<const uint32_t*>(d);
-                    a.nblk = cnt;
-                    return launch_groups();
-                });
-            if (rc) return rc;
-        }
+        if (rc) return rc;
     }
     return SHMR_EC_OK;
 }

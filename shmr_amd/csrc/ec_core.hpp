@@ -191,6 +191,10 @@ bool unaligned_vector(int dev);
 // INVALID_ARGUMENT; an invalidated capture: INVALID_ARGUMENT) is the caller's
 // status -- never taken for either answer.
 int capture_state(hipStream_t stream, bool* capturing);
+// device_init, then INVALID_ARGUMENT if `stream` is being captured: the entry
+// of every call that is not allowed inside a graph capture (shmr_ec.h), made
+// before it enqueues anything.
+int refuse_capture(int dev, hipStream_t stream);
 // The capture reserve (shmr_ec_capture_reserve): per-device pinned + device
 // memory for the tables of captured calls (shard-pointer tables of *_ptrs_dev,
 // block tables of multi-pattern reconstructs), which every replay re-reads.

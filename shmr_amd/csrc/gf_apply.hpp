@@ -282,24 +282,30 @@ struct KernelInfo {
 };
 size_t kernel_inventory(KernelInfo* out, size_t cap);
 
-// The parity check kernels (gf_verify.hip; ReedSolomon::verify): `a` as for an
-// encode launch of `rows` parity rows from a.row0 (single plan, strided blocks
-// blk_first + j * blk_stride, out_base = the STORED parity, which is only
-// read).  ORs bit min(a.row0 + r, 31) into mismatch[j] for every row r of
-// launch block j whose stored bytes differ from the recomputed ones in this
-// launch's tiles; writes nothing for a block without a difference.  mode 0:
-// full tiles of u = verify_chunks(rows) chunks per lane (the tools build:
-// 1 or 2); mode 1: one
-// partial tail tile per block; mode 2: byte-granular, any alignment.  One
-// workgroup per tile.  Not part of kernel_inventory.
+// The compare kernels (gf_compare.hip) share one body over the compare tile of
+// gf_syndrome.hpp: plan rows are recomputed from the k inputs and either
+// stored or compared with the bytes at their output slots.  Not part of
+// kernel_inventory.
+//
+// The parity check (ReedSolomon::verify): `a` as for an encode launch of `rows`
+// parity rows from a.row0 (single plan; a.blk_list must be null, else
+// hipErrorInvalidValue; out_base = the STORED parity, which is only read).  ORs bit min(a.row0 + r, 31) into mismatch[blk]
+// for every row r of a block whose stored bytes differ from the recomputed
+// ones in this launch's tiles; writes nothing for a block without a
+// difference.  blk = a.blk_first + j * a.blk_stride is the block's index, as
+// for launch_check below: the one caller (ec_core verify_on_device) launches
+// blk_first = 0, blk_stride = 1, so word j is launch block j's.  mode 0: full
+// tiles of u = verify_chunks(rows) chunks per lane (the tools build: 1 or 2);
+// mode 1: one partial tail tile per block; mode 2: byte-granular, any
+// alignment.  One workgroup per tile.
 // The measured tile size (profiles/r07/verify_ab*.jsonl): 8 KiB
 // full tiles (U = 2, wave-contiguous runs) at 3 and 4 rows, +1.4 / +1.7 points
 // of HBM peak over 4 KiB; 1 and 2 rows keep the encode policy's U = 1.
 constexpr int verify_chunks(unsigned rows) { return rows >= 3 ? 2 : 1; }
 hipError_t launch_verify(const ApplyArgs& a, uint32_t* mismatch, unsigned rows, int u, int mode, hipStream_t stream);
 
-// The checked-reconstruct kernels (gf_check.hip;
-// shmr_ec_reconstruct_checked_batch_dev): `a` as for an in-place reconstruct
+// The checked reconstruct (shmr_ec_reconstruct_checked_batch_dev): `a` as for
+// an in-place reconstruct
 // launch of `rows` plan rows from a.row0 (single plan; blocks blk_first + j *
 // blk_stride, or a.blk_list[j]; in_base == out_base, out_bias 0).  Rows
 // [0, nstore) of the group are computed and stored to their out_idx slots (absent
@@ -309,7 +315,7 @@ hipError_t launch_verify(const ApplyArgs& a, uint32_t* mismatch, unsigned rows, 
 // index as above -- not its position in the launch.  Writes no word of a
 // block without a difference.  mode 0: full 4 KiB tiles; mode 1: one partial
 // tail tile per block; mode 2: byte-granular, any alignment.  One workgroup per
-// tile.  Not part of kernel_inventory.
+// tile.
 hipError_t launch_check(const ApplyArgs& a, uint32_t* mismatch, unsigned rows, unsigned nstore, const uint32_t* bits,
                         int mode, hipStream_t stream);
 

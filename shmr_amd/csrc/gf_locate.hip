@@ -1,6 +1,6 @@
 // GF(2^8) single-shard location kernels for gfx950 (MI355X / CDNA4): the second
 // half of a scrub (shmr_ec_locate_batch_dev), behind the parity check of
-// gf_verify.hip.
+// gf_compare.hip.
 //
 //   cand[j] bit t stays set  <=>  in every column of block j,
 //   s_r == q[r][t] (x) s_0 for r = 1 .. R-1,   s = C (x) data ^ stored parity
@@ -31,7 +31,7 @@
 // and not part of shmr_ec_kernel_inventory.
 #include <hip/hip_runtime.h>
 
-#include "gf_tile.hpp"
+#include "gf_syndrome.hpp"
 #include "locate_plan.hpp"
 
 namespace shmr {
@@ -40,9 +40,13 @@ namespace kern {
 namespace {
 
 // The lane's syndrome chunk of every row: s[r] = XOR_t C[r][t] (x) data[t] ^ stored[r].
+// Not gf_syndrome.hpp's tile: its stored-row loads in the ring's look-ahead
+// slot cost this kernel 10 to 28 VGPRs, and with them the residency of its
+// bounded grid -- measured 0.9 % on a CLEAN batch, the case this kernel is
+// built for.  Here the stored rows are loaded behind the ring.
 template <int R, int MODE>
-__device__ __forceinline__ void syndrome_tile(const ApplyArgs& a, const Ctx& c, const uint8_t* ib, const uint8_t* ob,
-                                              uint64_t col, uint32_t (&s)[R][4]) {
+__device__ __forceinline__ void locate_syndromes(const ApplyArgs& a, const Ctx& c, const uint8_t* ib, const uint8_t* ob,
+                                                 uint64_t col, uint32_t (&s)[R][4]) {
     const uint64_t len = a.len;
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -79,7 +83,7 @@ struct LocateArgs {
 };
 
 // LDS: the staged encode plan of R rows (gf_tile.hpp stage_plan), then the ratio tables.
-__host__ __device__ inline uint32_t ratio_tab_off(uint32_t k, uint32_t R) { return (k * R * 32 + k * 8 + R * 8 + 15) & ~15u; }
+__host__ __device__ inline uint32_t ratio_tab_off(uint32_t k, uint32_t R) { return (plan_lds_bytes(k, R) + 15) & ~15u; }
 
 template <int R, int MODE>
 __global__ __launch_bounds__(kThreads) void gf_locate_kernel(const LocateArgs la) {
@@ -108,7 +112,7 @@ __global__ __launch_bounds__(kThreads) void gf_locate_kernel(const LocateArgs la
         const uint8_t* ib = a.in_base + blk * a.in_bpitch;
         const uint8_t* ob = a.out_base + blk * a.out_bpitch;
         uint32_t s[R][4];
-        syndrome_tile<R, MODE>(a, c, ib, ob, a.col_base + cc * tb + uint64_t(threadIdx.x) * 16, s);
+        locate_syndromes<R, MODE>(a, c, ib, ob, a.col_base + cc * tb + uint64_t(threadIdx.x) * 16, s);
         uint32_t any = 0;
 #pragma unroll
         for (int r = 0; r < R; ++r) any |= s[r][0] | s[r][1] | s[r][2] | s[r][3];
@@ -175,18 +179,14 @@ template <int R, int MODE>
 hipError_t launch_locate_one(const LocateArgs& la, hipStream_t stream) {
     const ApplyArgs& a = la.a;
     const size_t lds = size_t(ratio_tab_off(a.k, R)) + size_t(a.k) * (R - 1) * 32;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gf_locate_kernel<R, MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return e;
-    }
-    uint64_t grid = 0;
-    const hipError_t ge = locate_grid(&grid);
-    if (ge != hipSuccess) return ge;
-    if (grid > a.ntiles) grid = a.ntiles;
-    if (grid == 0) return hipSuccess;
+    uint64_t wgs = 0;
+    hipError_t e = locate_grid(&wgs);
+    if (e != hipSuccess) return e;
+    uint32_t grid = 0;
+    e = prepare_launch(reinterpret_cast<const void*>(gf_locate_kernel<R, MODE>), lds, a.ntiles, &grid, wgs);
+    if (e != hipSuccess || grid == 0) return e;
     // (by name, never through a function-pointer variable: gf_tile.hpp launch_one)
-    hipLaunchKernelGGL((gf_locate_kernel<R, MODE>), dim3(uint32_t(grid)), dim3(kThreads), lds, stream, la);
+    hipLaunchKernelGGL((gf_locate_kernel<R, MODE>), dim3(grid), dim3(kThreads), lds, stream, la);
     return hipGetLastError();
 }
 

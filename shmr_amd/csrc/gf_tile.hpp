@@ -447,13 +447,16 @@ __device__ __forceinline__ void do_tile(const ApplyArgs& a, const Ctx& c, const 
     store_rows<R, U, TH, MODE, F>(ob, c, col0, len, tid, acc);
 }
 
+// Bytes of R rows of a plan image staged in LDS (stage_plan):
+// [tables k*R*32 B][in_off k*8 B][out_off R*8 B].
+__host__ __device__ inline uint32_t plan_lds_bytes(uint32_t k, uint32_t R) { return k * R * 32 + k * 8 + R * 8; }
+
 // Byte offset of the LDS input ring (tools, kGlds) behind the staged plan.
 __host__ __device__ inline uint32_t glds_ring_off(uint32_t k, uint32_t R) {
-    return (k * R * 32 + k * 8 + R * 8 + 255) & ~255u;
+    return (plan_lds_bytes(k, R) + 255) & ~255u;
 }
 
-// Stages rows [row0, row0 + R) of a plan image into LDS:
-// [tables k*R*32 B][in_off k*8 B][out_off R*8 B].
+// Stages rows [row0, row0 + R) of a plan image into LDS (plan_lds_bytes).
 template <int R, int TH, bool PTRS>
 __device__ __forceinline__ void stage_plan(const ApplyArgs& a, const uint8_t* plan, uint8_t* smem, Ctx& c,
                                            uint64_t blk) {
@@ -773,7 +776,7 @@ __global__ __launch_bounds__(threads_of<F>(), occ_of<F>() ? occ_of<F>() : 1) voi
 template <int R, int U, int MODE, int F>
 hipError_t launch_one(const ApplyArgs& a, const Variant& v, int grid_cap, hipStream_t stream) {
     auto kern = gf_apply_kernel<R, U, MODE, F>;
-    size_t lds = (F & kSPre) ? 0 : size_t(a.k) * R * 32 + size_t(a.k) * 8 + size_t(R) * 8;
+    size_t lds = (F & kSPre) ? 0 : plan_lds_bytes(a.k, R);
     if constexpr ((F & kGlds) != 0)
         lds = glds_ring_off(a.k, R) + size_t(depth_of<F>()) * U * threads_of<F>() * 16;
     // Optional occupancy cap: pad the LDS allocation so at most wgs_per_cu

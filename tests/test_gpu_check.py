@@ -1,4 +1,4 @@
-"""Checked reconstruct on the GPU (gf_check.hip through
+"""Checked reconstruct on the GPU (gf_compare.hip through
 shmr_ec_reconstruct_checked_batch_dev) against oracle/rs_oracle.py.
 
 Layout of every case: B = 6 blocks of k + p shards in one device buffer with

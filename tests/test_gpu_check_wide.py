@@ -43,7 +43,7 @@ pytestmark = pytest.mark.gpu
 
 # ---- the product constants under test, mirrored once ----------------------------
 SLOT_BYTES = 256 * 1024     # ec_core.hpp:353  UploadRing::kSlotBytes
-CAP = SLOT_BYTES // 4       # ec_core.cpp:1466 checked_on_device: u32 block indices per part
+CAP = SLOT_BYTES // 4       # ec_core.cpp with_block_lists: u32 block indices per part
 MAX_ROWS = 4                # gf_apply.hpp     kern::kMaxRowsPerLaunch
 
 # ---- A1: the absent shards of every pattern, RS(4,4) ----------------------------

@@ -1,4 +1,4 @@
-"""ReedSolomon::verify on the GPU (gf_verify.hip through
+"""ReedSolomon::verify on the GPU (gf_compare.hip through
 shmr_ec_verify_batch_dev / shmr_ec_verify) against the CPU oracle.
 
 Codewords come from oracle.c_oracle.encode_batch; they are damaged on the
