@@ -457,6 +457,90 @@ int shmr_ec_checked_plan(shmr_ec_t* rs, const uint8_t* present, size_t nshards, 
                          uint16_t* in_idx, uint16_t* out_idx, uint8_t* out_rows,
                          size_t out_rows_len, uint32_t* n_store, uint32_t* n_check);
 
+/* ---- degraded blocks: locate a damaged survivor, and rebuild around it ------- *
+ * The checked reconstruct says that a survivor of a degraded block is damaged;
+ * these calls say which one, where the code can, and rebuild the block from
+ * the others.  Per block with np present shards, s = np - data surplus shards
+ * and D = M[surplus] * inv(M[inputs]) (one row per surplus shard, the rows the
+ * check compares): the inputs and the surplus shards are an MDS code of their
+ * own, so with the syndrome s_r of surplus row r
+ *   - surplus shard data + r damaged: only its row differs (the word has
+ *     exactly its bit);
+ *   - input t damaged: every compared row differs (the word is
+ *     shmr_ec_checked_rows of the pattern), and in every column
+ *     s_r == (D[r][t] / D[0][t]) * s_0.
+ * located[b] is SHMR_EC_LOCATE_CLEAN (the word is 0; also a block with s == 0,
+ * where nothing was compared -- as the checked reconstruct reports it), the
+ * index in [0, total) of the one present shard whose damage explains the block,
+ * or SHMR_EC_LOCATE_NONE.  A block with every shard present gets exactly
+ * shmr_ec_locate_batch_dev's answer.
+ * What the answer promises:
+ *   - s >= 3: damage in two survivors is never taken for damage in one.
+ *   - s == 2: damage in two survivors in the same column can pass for damage
+ *     in a third (distance 3).  Damage in different columns cannot.
+ *   - s <= 1: nothing is located; a non-zero word gives SHMR_EC_LOCATE_NONE (one
+ *     row cannot tell its own shard from an input).
+ *   - inputs are told apart by the first min(s, 4) surplus rows only.  Damage
+ *     in one input plus surplus rows beyond that group is reported as the
+ *     input; shmr_ec_reconstruct_repair_batch_dev catches it with its closing
+ *     verify.
+ *
+ * shmr_ec_locate_checked_batch_dev: shmr_ec_reconstruct_checked_batch_dev with
+ * the same addressing, `present`, `flags` and counters -- d_mismatch receives
+ * that call's words unchanged, the shards what that call writes -- plus
+ * d_located (nblocks int32, device) and d_work, work_bytes >=
+ * shmr_ec_locate_work_size(rs, nblocks) bytes of device scratch (4-byte
+ * aligned).  Needs 2 <= parity <= 32 (INVALID_ARGUMENT otherwise, before
+ * anything else is looked at).  Checked in that call's order, the scratch with
+ * the pointers.  Behind the check's kernels: per presence pattern with s >= 2
+ * a read-only kernel (one word per tile of a block whose word is not the
+ * pattern's row mask; the inputs and the first min(s, 4) surplus shards of the
+ * others) and per pattern an O(nblocks) kernel that writes the answers.  One
+ * more SHMR_EC_DEV_LAUNCHES per pattern with s >= 2.  Stream-ordered, no
+ * allocation and no host readback.  NOT capturable (INVALID_ARGUMENT, nothing
+ * enqueued). */
+int shmr_ec_locate_checked_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard_pitch,
+                                     size_t block_pitch, const uint8_t* present, size_t nblocks,
+                                     size_t shard_len, int flags, uint32_t* d_mismatch,
+                                     int32_t* d_located, void* d_work, size_t work_bytes,
+                                     int device, void* stream);
+
+/* The whole repair, blocking (NOT stream-ordered, NOT capturable: it waits on
+ * `stream` twice and takes pooled device scratch), built as
+ * shmr_ec_scrub_batch_dev: the locate above with flags 0 (every absent shard
+ * rebuilt at the checked reconstruct's one pass); the answers copied to the
+ * host; for each block with a located shard, its absent shards and the located
+ * one rebuilt through shmr_ec_reconstruct_batch_dev's path (present = the
+ * given flags minus the located shard: at least `data` remain, since s >= 2);
+ * a verify of the whole batch, every slot having been written; a repaired
+ * block that still differs demoted to SHMR_EC_LOCATE_NONE (its located shard
+ * has been rewritten).  A block that locate reports as SHMR_EC_LOCATE_NONE
+ * keeps its present shards byte for byte; its absent slots hold the suspect
+ * rebuild, the checked reconstruct's contract.
+ * located_host: nblocks int32 of HOST memory, or NULL.  counts (HOST, 3
+ * entries): blocks clean, repaired, not repairable; written (zeroed first)
+ * only once the arguments and the device have been accepted, so a refused
+ * call leaves them alone.  Checked in this order: NULL rs or counts, or a
+ * codec outside 2 <= parity <= 32 (INVALID_ARGUMENT); nblocks == 0 (OK);
+ * shard_len == 0 (EMPTY_SHARD); a NULL d_shards or present (INVALID_ARGUMENT);
+ * a block with fewer than `data` present (TOO_FEW_SHARDS_PRESENT); the device. */
+int shmr_ec_reconstruct_repair_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard_pitch,
+                                         size_t block_pitch, const uint8_t* present,
+                                         size_t nblocks, size_t shard_len, int32_t* located_host,
+                                         uint64_t* counts, int device, void* stream);
+
+/* Host only; for tests and tools (as shmr_ec_checked_plan): what the degraded
+ * locate runs for a presence pattern.  in_idx (data entries): the inputs;
+ * out_idx (total entries, the first s used): the s surplus shards, ascending;
+ * ratio_rows: *n_rows rows of `data` entries, row r-1 entry t =
+ * D[r][t] / D[0][t], *n_rows = min(s, 4) - 1, or 0 for s < 2 (nothing can be
+ * located); *row_mask: shmr_ec_checked_rows of the pattern.  ratio_rows_len <
+ * *n_rows * data, or a pattern with a zero D[0][t] (none of this matrix has
+ * one): INVALID_ARGUMENT.  Counts and presence as shmr_ec_reconstruct_plan. */
+int shmr_ec_locate_checked_plan(shmr_ec_t* rs, const uint8_t* present, size_t nshards,
+                                uint16_t* in_idx, uint16_t* out_idx, uint8_t* ratio_rows,
+                                size_t ratio_rows_len, uint32_t* n_rows, uint32_t* row_mask);
+
 /* Reconstruct with the crate's memory semantics: every absent shard is
  * rebuilt into a buffer of its own (reed_solomon_erasure allocates
  * vec![0; len] for each None, called at src/vfs/block.rs:556-565; load_block

@@ -80,6 +80,15 @@ SIGNATURES = [
     ("shmr_ec_checked_plan", ctypes.c_int,
      [ctypes.c_void_p, _u8p, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(ctypes.c_uint16),
       _u8p, _sz, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    ("shmr_ec_locate_checked_batch_dev", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, _sz, ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_reconstruct_repair_batch_dev", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.POINTER(ctypes.c_int32),
+      ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_locate_checked_plan", ctypes.c_int,
+     [ctypes.c_void_p, _u8p, _sz, ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(ctypes.c_uint16), _u8p, _sz,
+      ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     ("shmr_ec_reconstruct_batch_dev_out", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_int, ctypes.c_void_p, _sz, _sz,
       ctypes.c_int, ctypes.c_void_p]),

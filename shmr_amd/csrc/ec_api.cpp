@@ -20,6 +20,7 @@
 
 #include "ec_core.hpp"
 #include "host_engine.hpp"
+#include "locate_plan.hpp"
 #include "submit.hpp"
 
 using shmr::core::Codec;
@@ -1094,6 +1095,131 @@ int shmr_ec_checked_plan(shmr_ec_t* rs, const uint8_t* present, size_t nshards, 
         *n_store = plan->m - plan->n_check;
         *n_check = plan->n_check;
         return SHMR_EC_OK;
+    });
+}
+
+// ---- degraded blocks: locate a damaged survivor, and rebuild around it ---------------
+int shmr_ec_locate_checked_plan(shmr_ec_t* rs, const uint8_t* present, size_t nshards, uint16_t* in_idx,
+                                uint16_t* out_idx, uint8_t* ratio_rows, size_t ratio_rows_len, uint32_t* n_rows,
+                                uint32_t* row_mask) {
+    return guarded_light([&]() -> int {
+        if (!rs || !present || !in_idx || !out_idx || !ratio_rows || !n_rows || !row_mask) return SHMR_EC_INVALID_ARGUMENT;
+        const int rc = check_pattern(rs, present, nshards);
+        if (rc) return rc;
+        const unsigned k = rs->codec->k(), t = k + rs->codec->p();
+        std::vector<uint8_t> pr(present, present + t);
+        const auto cp = rs->codec->checked_plan(pr, false, true);
+        const unsigned s = cp->n_check;
+        bool singular = false;
+        const auto lp = rs->codec->locate_checked_plan(pr, &singular);
+        if (singular) return SHMR_EC_INVALID_ARGUMENT;
+        const unsigned rows = lp ? lp->m : 0;
+        if (ratio_rows_len < size_t(rows) * k) return SHMR_EC_INVALID_ARGUMENT;
+        std::memcpy(in_idx, cp->in_idx.data(), 2 * size_t(k));
+        if (s) std::memcpy(out_idx, cp->out_idx.data(), 2 * size_t(s));
+        if (rows) std::memcpy(ratio_rows, lp->rows.d.data(), size_t(rows) * k);
+        *n_rows = rows;
+        *row_mask = shmr::locate::row_mask(cp->out_idx.data(), s, k);
+        return SHMR_EC_OK;
+    });
+}
+
+int shmr_ec_locate_checked_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard_pitch, size_t block_pitch,
+                                     const uint8_t* present, size_t nblocks, size_t shard_len, int flags,
+                                     uint32_t* d_mismatch, int32_t* d_located, void* d_work, size_t work_bytes,
+                                     int device, void* stream) {
+    return guarded([&]() -> int {
+        if (!rs || !rs->codec->locate_plan()) return SHMR_EC_INVALID_ARGUMENT;
+        Codec& c = *rs->codec;
+        const int known = SHMR_EC_CHECK_DATA_ONLY | SHMR_EC_CHECK_NO_REBUILD;
+        const bool given = d_shards && present && words_given(d_mismatch) && words_given(d_located) &&
+                           words_given(d_work) && work_bytes >= core::locate_work_bytes(c, nblocks) &&
+                           (flags & ~known) == 0;
+        // (no launch on a bad batch)
+        auto check = [&] { return given ? core::validate_presence(c, present, nblocks) : arg_ok(false); };
+        return batch_dev(nblocks, shard_len, device, check, [&] {
+            return core::locate_checked_on_device(c, device, d_shards, shard_pitch, block_pitch, present, nblocks,
+                                                  shard_len, (flags & SHMR_EC_CHECK_DATA_ONLY) != 0,
+                                                  (flags & SHMR_EC_CHECK_NO_REBUILD) != 0, d_mismatch, d_located,
+                                                  static_cast<uint32_t*>(d_work), static_cast<hipStream_t>(stream));
+        });
+    });
+}
+
+int shmr_ec_reconstruct_repair_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard_pitch, size_t block_pitch,
+                                         const uint8_t* present, size_t nblocks, size_t shard_len,
+                                         int32_t* located_host, uint64_t* counts, int device, void* stream_) {
+    return guarded([&]() -> int {
+        if (!rs || !counts || !rs->codec->locate_plan()) return SHMR_EC_INVALID_ARGUMENT;
+        // (counts are written only by a call that is accepted: an empty batch, or below)
+        if (nblocks == 0) counts[0] = counts[1] = counts[2] = 0;
+        Codec& c = *rs->codec;
+        hipStream_t stream = static_cast<hipStream_t>(stream_);
+        // (no launch on a bad batch)
+        auto check = [&] { return d_shards && present ? core::validate_presence(c, present, nblocks) : arg_ok(false); };
+        return batch_dev(nblocks, shard_len, device, check, [&]() -> int {
+            int rc = core::refuse_capture(device, stream);   // it waits for its own results
+            if (rc) return rc;
+            counts[0] = counts[1] = counts[2] = 0;
+            const unsigned k = c.k(), t = k + c.p();
+            // pooled scratch (grown without a free): the words, the answers, the candidate bitmaps
+            const size_t words_bytes = size_t(core::round_up(nblocks * sizeof(uint32_t), 256));
+            core::StagingLease lease;
+            lease.s = core::StagingPool::get().acquire(device, 2 * words_bytes + core::locate_work_bytes(c, nblocks), &rc);
+            if (!lease.s) return rc;
+            uint32_t* d_words = reinterpret_cast<uint32_t*>(lease.s->dbuf);
+            int32_t* d_located = reinterpret_cast<int32_t*>(lease.s->dbuf + words_bytes);
+            uint32_t* d_cand = reinterpret_cast<uint32_t*>(lease.s->dbuf + 2 * words_bytes);
+            // (a failure below still waits: the scratch goes back to the pool idle)
+            auto fetch = [&](void* dst, const void* src) -> int {
+                const hipError_t e = hipMemcpyAsync(dst, src, nblocks * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+                const hipError_t w = core::sync_stream(stream);
+                return e == hipSuccess && w == hipSuccess ? SHMR_EC_OK : SHMR_EC_DEVICE_ERROR;
+            };
+            std::vector<int32_t> own;
+            int32_t* located = located_host;
+            if (!located) {
+                own.resize(nblocks);
+                located = own.data();
+            }
+            // every absent shard rebuilt, every surplus shard compared, one pass
+            rc = core::locate_checked_on_device(c, device, d_shards, shard_pitch, block_pitch, present, nblocks,
+                                                shard_len, false, false, d_words, d_located, d_cand, stream);
+            const int frc = fetch(located, d_located);
+            if (rc || frc) return rc ? rc : frc;
+            // a located block: its absent shards (rebuilt above from a damaged input,
+            // where it was one) and the located shard, from the good survivors.
+            // Every other block counts as complete here: nothing to rebuild.
+            std::vector<size_t> hit;
+            std::vector<uint8_t> pr(nblocks * t, 1);
+            for (size_t b = 0; b < nblocks; ++b) {
+                if (located[b] < 0) {
+                    ++counts[located[b] == SHMR_EC_LOCATE_CLEAN ? 0 : 2];
+                    continue;
+                }
+                hit.push_back(b);
+                for (unsigned i = 0; i < t; ++i) pr[b * t + i] = present[b * t + i] ? 1 : 0;
+                pr[b * t + size_t(located[b])] = 0;
+            }
+            if (hit.empty()) return SHMR_EC_OK;
+            rc = core::reconstruct_on_device(c, device, d_shards, shard_pitch, block_pitch, pr.data(), nblocks, shard_len,
+                                             false, stream);
+            // the closing verify (every slot has been written by now): damage
+            // beyond what locate looked at shows here
+            if (rc == SHMR_EC_OK) {
+                const core::Layout L = batch_layout(c, d_shards, shard_pitch, block_pitch, d_shards + k * shard_pitch,
+                                                    shard_pitch, block_pitch);
+                rc = core::verify_on_device(c, device, L, nblocks, shard_len, d_words, stream);
+            }
+            std::vector<uint32_t> words(nblocks);
+            const int wrc = fetch(words.data(), d_words);
+            if (rc || wrc) return rc ? rc : wrc;
+            for (size_t b : hit) {
+                if (words[b] != 0) located[b] = SHMR_EC_LOCATE_NONE;
+                ++counts[words[b] != 0 ? 2 : 1];
+            }
+            return SHMR_EC_OK;
+        });
     });
 }
 

@@ -1484,6 +1484,96 @@ int checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch
 }
 
 // ===========================================================================
+// Single-shard location in degraded blocks.  The checked reconstruct above into
+// d_mismatch; the candidate bitmaps preset to all ones; then per presence
+// pattern, over the same blocks (by stride or block lists, as the check): for
+// s >= 2 surplus shards the degraded locate kernel over the first row group of
+// the pattern's compare-only checked plan, split as the check's launches
+// (4 KiB tiles); and for every pattern the degraded resolve kernel.  One more
+// launch group is counted per located pattern.
+// ===========================================================================
+int locate_checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch, uint64_t block_pitch,
+                             const uint8_t* present, uint64_t nblocks, uint64_t len, bool data_only, bool no_rebuild,
+                             uint32_t* d_mismatch, int32_t* d_located, uint32_t* d_cand, hipStream_t stream) {
+    const unsigned k = c.k();
+    // Not inside a graph capture (shmr_ec.h): refused before anything is enqueued.
+    int rc = refuse_capture(dev, stream);
+    if (rc) return rc;
+    if (nblocks == 0) return SHMR_EC_OK;
+    if (nblocks > 0xffffffffull) return SHMR_EC_INVALID_ARGUMENT;   // block lists are 32-bit
+    PatternGroups groups;
+    if ((rc = group_patterns(c, present, nblocks, nullptr, true, &groups))) return rc;
+    // every pattern's plans, before anything is enqueued
+    struct Located {
+        std::shared_ptr<Plan> compare, ratio;   // null below two surplus shards
+        unsigned s = 0;
+        uint32_t mask = 0;
+    };
+    std::vector<Located> plans;
+    for (auto& g : groups) {
+        Located lp;
+        const std::shared_ptr<Plan> cp = c.checked_plan(g.first, false, true);
+        lp.s = cp->n_check;
+        lp.mask = locate::row_mask(cp->out_idx.data(), lp.s, k);
+        if (lp.s >= 2) {
+            lp.compare = cp;
+            lp.ratio = c.locate_checked_plan(g.first);
+            if (!lp.ratio) return SHMR_EC_INVALID_ARGUMENT;   // some D[0][t] is 0: no ratio exists
+        }
+        plans.push_back(std::move(lp));
+    }
+    rc = checked_on_device(c, dev, d_shards, shard_pitch, block_pitch, present, nblocks, len, data_only, no_rebuild,
+                           d_mismatch, stream);
+    if (rc) return rc;
+    SHMR_HIP_TRY(kern::launch_locate_preset(d_cand, nblocks, k, stream));
+    const Layout L{d_shards, d_shards, block_pitch, shard_pitch, block_pitch, shard_pitch, 0};
+    size_t gi = 0;
+    for (auto& g : groups) {
+        const Located& lp = plans[gi++];
+        kern::ApplyArgs a{};
+        a.k = k;
+        const uint8_t *dplan = nullptr, *dratio = nullptr;
+        if (lp.s >= 2) {
+            if ((rc = plan_on_device(*lp.compare, dev, stream, false, &dplan))) return rc;
+            if ((rc = plan_on_device(*lp.ratio, dev, stream, false, &dratio))) return rc;
+            a = apply_args(L, *lp.compare, dplan, len);
+        }
+        // the pattern's locate (s >= 2) and resolve launches over the blocks `a` names
+        auto launch_pattern = [&]() -> int {
+            if (lp.s >= 2) {
+                const uint8_t* qtab = dratio + plan_tab_off(lp.ratio->k, lp.ratio->m);
+                const int lrc = compare_groups(dev, L, a, locate::rows_used(lp.s), len, tile_4k,
+                                               [&](uint32_t rows, uint32_t, int mode, int) {
+                                                   return kern::launch_locate_checked(a, qtab, d_mismatch, d_cand, rows,
+                                                                                      lp.mask, mode, stream);
+                                               });
+                if (lrc) return lrc;
+            }
+            SHMR_HIP_TRY(kern::launch_locate_checked_resolve(
+                a, d_mismatch, d_cand, d_located, dplan ? reinterpret_cast<const uint16_t*>(dplan + 8) : nullptr, lp.s,
+                lp.mask, stream));
+            return SHMR_EC_OK;
+        };
+        const std::vector<uint64_t>& blocks = g.second;
+        uint64_t stride = 1;
+        if (arith_stride(blocks.data(), blocks.size(), &stride)) {
+            a.blk_first = blocks[0];
+            a.blk_stride = stride;
+            a.nblk = blocks.size();
+            rc = launch_pattern();
+        } else {
+            rc = with_block_lists(dev, stream, blocks.data(), blocks.size(), [&](const uint32_t* d_list, uint64_t cnt) {
+                a.blk_list = d_list;
+                a.nblk = cnt;
+                return launch_pattern();
+            });
+        }
+        if (rc) return rc;
+    }
+    return SHMR_EC_OK;
+}
+
+// ===========================================================================
 // Upload ring
 // ===========================================================================
 UploadRing* UploadRing::for_device(int dev, int* rc, Kind kind) {

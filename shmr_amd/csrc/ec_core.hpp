@@ -334,6 +334,18 @@ int checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch
                       const uint8_t* present, uint64_t nblocks, uint64_t len, bool data_only, bool no_rebuild,
                       uint32_t* d_mismatch, hipStream_t stream);
 
+// Single-shard location in degraded blocks (shmr_ec_locate_checked_batch_dev):
+// checked_on_device with the same arguments, then d_located[b] =
+// locate::resolve_checked of block b's word, pattern and candidate bitmap
+// (d_cand: locate_work_bytes(c, nblocks) bytes of scratch).  A pattern with
+// fewer than two surplus shards locates nothing; a pattern whose ratios do not
+// exist is INVALID_ARGUMENT before anything is enqueued.  Stream-ordered, no
+// host readback, no allocation beyond plan and block-list uploads; a stream
+// that is being captured is refused.
+int locate_checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch, uint64_t block_pitch,
+                             const uint8_t* present, uint64_t nblocks, uint64_t len, bool data_only, bool no_rebuild,
+                             uint32_t* d_mismatch, int32_t* d_located, uint32_t* d_cand, hipStream_t stream);
+
 // A shard-pointer table call (ptrs.cpp): tab[b * total + i] is the device
 // address of shard i of block b (0 for a shard the call does not touch),
 // validated by the caller.  A table on a slot lattice runs the strided kernels

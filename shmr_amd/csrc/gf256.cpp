@@ -289,6 +289,35 @@ std::shared_ptr<Plan> Codec::checked_plan(const std::vector<uint8_t>& present, b
     return plan;
 }
 
+std::shared_ptr<Plan> Codec::locate_checked_plan(const std::vector<uint8_t>& present, bool* singular) {
+    if (singular) *singular = false;
+    // The compare-only checked plan: its rows are D, one per surplus shard.
+    const std::shared_ptr<Plan> cp = checked_plan(present, false, true);
+    const unsigned s = cp->n_check;
+    if (s < 2) return nullptr;
+    // (key[t + 1] = 4: never a checked_plan or reconstruct_plan key)
+    const unsigned t = k_ + p_;
+    std::vector<uint8_t> key(t + 2, 0);
+    for (unsigned i = 0; i < t; ++i) key[i] = present[i] ? 1 : 0;
+    key[t + 1] = 4;
+    std::lock_guard<std::mutex> lock(mu_);
+    auto found = plans_.find(key);
+    if (found != plans_.end()) return found->second;
+    const unsigned R = locate::rows_used(s);
+    auto lp = std::make_shared<Plan>();
+    lp->k = k_;
+    lp->m = R - 1;
+    lp->rows = Matrix(R - 1, k_);
+    if (!locate::ratio_rows(cp->rows.row(cp->m - s), k_, R, div, lp->rows.d.data())) {
+        if (singular) *singular = true;
+        return nullptr;
+    }
+    lp->in_idx = cp->in_idx;
+    for (unsigned r = 1; r < R; ++r) lp->out_idx.push_back(cp->out_idx[cp->m - s + r]);   // (unused: nothing is stored)
+    plans_[key] = lp;
+    return lp;
+}
+
 std::shared_ptr<Codec> get_codec(unsigned k, unsigned p) {
     // Leaked on purpose: codecs own device images that must outlive every
     // in-flight kernel, and HIP may already be torn down at static exit.

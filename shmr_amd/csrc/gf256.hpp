@@ -124,6 +124,14 @@ public:
     // is the identity and they are the encode rows.  Cached per pattern.
     std::shared_ptr<Plan> checked_plan(const std::vector<uint8_t>& present, bool data_only, bool no_rebuild);
 
+    // The ratio rows of single-shard location in a degraded block
+    // (locate_plan.hpp), in the shape of locate_plan(): the k inputs of
+    // checked_plan(present), min(s, 4) - 1 rows, row r-1 entry t =
+    // D[r][t] / D[0][t], D the s compare rows of that plan.  Null for s < 2
+    // (nothing can be located), and with *singular set where some D[0][t] is 0
+    // (no pattern of this matrix has one).  Cached per pattern.
+    std::shared_ptr<Plan> locate_checked_plan(const std::vector<uint8_t>& present, bool* singular = nullptr);
+
     uint64_t decode_cache_hits() const { return hits_; }
     uint64_t decode_cache_misses() const { return misses_; }
 

@@ -337,6 +337,24 @@ hipError_t launch_locate_preset(uint32_t* cand, uint64_t nblk, unsigned k, hipSt
 hipError_t launch_locate_resolve(const uint32_t* mismatch, const uint32_t* cand, int32_t* located, uint64_t nblk,
                                  unsigned k, unsigned p, hipStream_t stream);
 
+// The degraded forms (shmr_ec_locate_checked_batch_dev), behind a launch_check
+// of the same blocks: `a` as for launch_check of the pattern's compare-only
+// checked plan (in_base == out_base, a.row0 = 0; blocks blk_first + j *
+// blk_stride, or a.blk_list[j]), rows = min(s, 4) in [2, 4] of its s = a.m
+// compare rows; row_mask the word of a block whose every compared row differs;
+// qtab the tables of the pattern's ratio plan (PermTab[k][rows - 1]).
+// mismatch and cand are indexed by the block's index in the batch, not by j.
+// Reads the k inputs and the first `rows` surplus shards of a block whose word
+// is row_mask, one word per tile of any other; stores nothing but the atomics.
+hipError_t launch_locate_checked(const ApplyArgs& a, const uint8_t* qtab, const uint32_t* mismatch, uint32_t* cand,
+                                 unsigned rows, uint32_t row_mask, int mode, hipStream_t stream);
+// located[blk] = locate::resolve_checked(mismatch[blk], cand + blk * words, k, s, row_mask, idx, idx + k) for
+// the blocks `a` names.  idx: in_idx[k] then out_idx[s] in device memory (the
+// header of the compare-only plan image, + 8); may be null for s < 2.
+hipError_t launch_locate_checked_resolve(const ApplyArgs& a, const uint32_t* mismatch, const uint32_t* cand,
+                                         int32_t* located, const uint16_t* idx, unsigned s, uint32_t row_mask,
+                                         hipStream_t stream);
+
 // The parity delta update kernel (gf_update.hip; shmr_ec_update_batch_dev):
 // one launch over pieces [0, npieces) of a piece table (update_plan.hpp
 // DevPiece, device memory), all of one round: no two of them store to the same

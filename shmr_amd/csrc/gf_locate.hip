@@ -26,6 +26,12 @@
 //    MODE 2 byte-granular at any alignment: bytes at or past len are read by
 //    neither side (both are zero there, as in the parity check).
 //  * The resolve kernel: one thread per block, locate::resolve.
+//  * Degraded blocks (shmr_ec_locate_checked_batch_dev): gf_locate_checked_kernel
+//    and gf_locate_checked_resolve_kernel, launched per presence pattern behind
+//    the checked reconstruct of gf_compare.hip.  The same tile loop as a
+//    separate instantiation (locate_tiles<.., DEG>): the pattern's compare rows
+//    D in place of C, its blocks by stride or list, its row mask in the skip
+//    test; locate::resolve_checked.
 //
 // Like the parity check kernels these are not gf_apply_kernel instantiations
 // and not part of shmr_ec_kernel_inventory.
@@ -85,12 +91,18 @@ struct LocateArgs {
 // LDS: the staged encode plan of R rows (gf_tile.hpp stage_plan), then the ratio tables.
 __host__ __device__ inline uint32_t ratio_tab_off(uint32_t k, uint32_t R) { return (plan_lds_bytes(k, R) + 15) & ~15u; }
 
-template <int R, int MODE>
-__global__ __launch_bounds__(kThreads) void gf_locate_kernel(const LocateArgs la) {
+// The tile loop of both locate kernels.  DEG (degraded blocks,
+// shmr_ec_locate_checked_batch_dev): the launch names the blocks of one
+// presence pattern -- blk_first + j * blk_stride, or blk_list[j] -- and the
+// verify word and the bitmap are the block's own (index blk, not j); `a` is the
+// pattern's compare-only checked plan, so inputs and stored rows go through its
+// in_idx / out_idx offsets, and all_rows is the pattern's row mask.  A template
+// flag, not a launch argument: the complete-block kernel carries none of it.
+template <int R, int MODE, bool DEG>
+__device__ __forceinline__ void locate_tiles(const LocateArgs& la, uint8_t* smem) {
     constexpr int TH = kThreads;
     constexpr int Q = R - 1;
     const ApplyArgs& a = la.a;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t k = a.k;
     Ctx c{}, qc{};
     bool staged = false;
@@ -98,7 +110,10 @@ __global__ __launch_bounds__(kThreads) void gf_locate_kernel(const LocateArgs la
     const uint32_t tpb = a.tiles_per_block;
     for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
         const uint64_t j = tile / tpb, cc = tile - j * tpb;
-        if (as_const<cu32>(la.mismatch)[j] != la.all_rows) continue;   // clean, or parity rows only
+        uint64_t w = j;   // the block's index in the batch
+        if constexpr (DEG)
+            w = a.blk_list ? uint64_t(as_const<cu32>(a.blk_list)[j]) : a.blk_first + j * a.blk_stride;
+        if (as_const<cu32>(la.mismatch)[w] != la.all_rows) continue;   // clean, or stored rows only
         if (!staged) {   // (workgroup-uniform: every lane of the workgroup is here)
             stage_plan<R, TH, false>(a, a.plan, smem, c, 0);
             u32x4* s_q = reinterpret_cast<u32x4*>(smem + ratio_tab_off(k, R));
@@ -108,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void gf_locate_kernel(const LocateArgs la
             __syncthreads();
             staged = true;
         }
-        const uint64_t blk = a.blk_first + j * a.blk_stride;
+        const uint64_t blk = DEG ? w : a.blk_first + j * a.blk_stride;
         const uint8_t* ib = a.in_base + blk * a.in_bpitch;
         const uint8_t* ob = a.out_base + blk * a.out_bpitch;
         uint32_t s[R][4];
@@ -119,7 +134,7 @@ __global__ __launch_bounds__(kThreads) void gf_locate_kernel(const LocateArgs la
         // every lane of the wave is here (no lane leaves a tile early); no barrier follows
         if (__builtin_amdgcn_ballot_w64(any != 0) == 0) continue;   // this wave's columns eliminate nobody
         const u32x4 s0{s[0][0], s[0][1], s[0][2], s[0][3]};
-        uint32_t* bw = la.cand + j * la.words;
+        uint32_t* bw = la.cand + w * la.words;
         uint32_t keep = 0xffffffffu;   // wave-uniform: the survivors among shards [t & ~31, t]
         for (uint32_t t = 0; t < k; ++t) {
             Tab tq[Q];
@@ -144,6 +159,18 @@ __global__ __launch_bounds__(kThreads) void gf_locate_kernel(const LocateArgs la
     }
 }
 
+template <int R, int MODE>
+__global__ __launch_bounds__(kThreads) void gf_locate_kernel(const LocateArgs la) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    locate_tiles<R, MODE, false>(la, smem);
+}
+
+template <int R, int MODE>
+__global__ __launch_bounds__(kThreads) void gf_locate_checked_kernel(const LocateArgs la) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    locate_tiles<R, MODE, true>(la, smem);
+}
+
 // Every data shard of every block is a candidate until a tile rules it out.
 // (A kernel: a hipMemsetAsync of 0xff did the same eagerly, but as a memset
 // node of a captured graph it left other bytes behind on replay)
@@ -158,6 +185,29 @@ __global__ __launch_bounds__(kThreads) void gf_locate_resolve_kernel(const uint3
     const uint64_t b = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
     if (b >= nblk) return;
     located[b] = locate::resolve(mismatch[b], cand + b * locate::bitmap_words(k), k, p);
+}
+
+// The degraded form: one thread per block of a pattern's launch (blocks as in
+// locate_tiles<.., DEG>), locate::resolve_checked over the pattern's s, row
+// mask and index maps.  idx: in_idx[k] then out_idx[s], the header of the
+// pattern's compare-only plan image; null for s < 2, where the answer comes
+// from the word alone and no map is read.
+struct ResolveCheckedArgs {
+    const uint32_t* mismatch;
+    const uint32_t* cand;
+    int32_t* located;
+    const uint32_t* blk_list;
+    uint64_t blk_first, blk_stride, nblk;
+    const uint16_t* idx;
+    uint32_t k, s, mask;
+};
+
+__global__ __launch_bounds__(kThreads) void gf_locate_checked_resolve_kernel(const ResolveCheckedArgs ra) {
+    const uint64_t j = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+    if (j >= ra.nblk) return;
+    const uint64_t b = ra.blk_list ? uint64_t(ra.blk_list[j]) : ra.blk_first + j * ra.blk_stride;
+    ra.located[b] = locate::resolve_checked(ra.mismatch[b], ra.cand + b * locate::bitmap_words(ra.k), ra.k, ra.s,
+                                            ra.mask, ra.idx, ra.idx + ra.k);
 }
 
 // Workgroups of a locate launch: the tile loop strides over them.  A clean
@@ -175,7 +225,7 @@ hipError_t locate_grid(uint64_t* grid) {
     return hipSuccess;
 }
 
-template <int R, int MODE>
+template <int R, int MODE, bool DEG>
 hipError_t launch_locate_one(const LocateArgs& la, hipStream_t stream) {
     const ApplyArgs& a = la.a;
     const size_t lds = size_t(ratio_tab_off(a.k, R)) + size_t(a.k) * (R - 1) * 32;
@@ -183,19 +233,35 @@ hipError_t launch_locate_one(const LocateArgs& la, hipStream_t stream) {
     hipError_t e = locate_grid(&wgs);
     if (e != hipSuccess) return e;
     uint32_t grid = 0;
-    e = prepare_launch(reinterpret_cast<const void*>(gf_locate_kernel<R, MODE>), lds, a.ntiles, &grid, wgs);
-    if (e != hipSuccess || grid == 0) return e;
     // (by name, never through a function-pointer variable: gf_tile.hpp launch_one)
-    hipLaunchKernelGGL((gf_locate_kernel<R, MODE>), dim3(grid), dim3(kThreads), lds, stream, la);
+    if constexpr (DEG) {
+        e = prepare_launch(reinterpret_cast<const void*>(gf_locate_checked_kernel<R, MODE>), lds, a.ntiles, &grid, wgs);
+        if (e != hipSuccess || grid == 0) return e;
+        hipLaunchKernelGGL((gf_locate_checked_kernel<R, MODE>), dim3(grid), dim3(kThreads), lds, stream, la);
+    } else {
+        e = prepare_launch(reinterpret_cast<const void*>(gf_locate_kernel<R, MODE>), lds, a.ntiles, &grid, wgs);
+        if (e != hipSuccess || grid == 0) return e;
+        hipLaunchKernelGGL((gf_locate_kernel<R, MODE>), dim3(grid), dim3(kThreads), lds, stream, la);
+    }
     return hipGetLastError();
 }
 
-template <int R>
+template <int R, bool DEG>
 hipError_t dispatch_locate(const LocateArgs& la, int mode, hipStream_t stream) {
     switch (mode) {
-        case 0: return launch_locate_one<R, 0>(la, stream);
-        case 1: return launch_locate_one<R, 1>(la, stream);
-        case 2: return launch_locate_one<R, 2>(la, stream);
+        case 0: return launch_locate_one<R, 0, DEG>(la, stream);
+        case 1: return launch_locate_one<R, 1, DEG>(la, stream);
+        case 2: return launch_locate_one<R, 2, DEG>(la, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+template <bool DEG>
+hipError_t dispatch_locate_rows(const LocateArgs& la, unsigned rows, int mode, hipStream_t stream) {
+    switch (rows) {
+        case 2: return dispatch_locate<2, DEG>(la, mode, stream);
+        case 3: return dispatch_locate<3, DEG>(la, mode, stream);
+        case 4: return dispatch_locate<4, DEG>(la, mode, stream);
         default: return hipErrorInvalidValue;
     }
 }
@@ -211,12 +277,42 @@ hipError_t launch_locate(const ApplyArgs& a, const uint8_t* qtab, const uint32_t
     la.cand = cand;
     la.all_rows = locate::all_rows(p);
     la.words = locate::bitmap_words(a.k);
-    switch (rows) {
-        case 2: return dispatch_locate<2>(la, mode, stream);
-        case 3: return dispatch_locate<3>(la, mode, stream);
-        case 4: return dispatch_locate<4>(la, mode, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_locate_rows<false>(la, rows, mode, stream);
+}
+
+hipError_t launch_locate_checked(const ApplyArgs& a, const uint8_t* qtab, const uint32_t* mismatch, uint32_t* cand,
+                                 unsigned rows, uint32_t row_mask, int mode, hipStream_t stream) {
+    if (a.row0 != 0 || rows > a.m) return hipErrorInvalidValue;   // the first rows of the pattern's compare rows
+    LocateArgs la;
+    la.a = a;
+    la.qtab = qtab;
+    la.mismatch = mismatch;
+    la.cand = cand;
+    la.all_rows = row_mask;
+    la.words = locate::bitmap_words(a.k);
+    return dispatch_locate_rows<true>(la, rows, mode, stream);
+}
+
+hipError_t launch_locate_checked_resolve(const ApplyArgs& a, const uint32_t* mismatch, const uint32_t* cand,
+                                         int32_t* located, const uint16_t* idx, unsigned s, uint32_t row_mask,
+                                         hipStream_t stream) {
+    const uint64_t grid = (a.nblk + kThreads - 1) / kThreads;
+    if (grid == 0) return hipSuccess;
+    if (grid > 0x7fffffffull || (s >= 2 && !idx)) return hipErrorInvalidValue;
+    ResolveCheckedArgs ra;
+    ra.mismatch = mismatch;
+    ra.cand = cand;
+    ra.located = located;
+    ra.blk_list = a.blk_list;
+    ra.blk_first = a.blk_first;
+    ra.blk_stride = a.blk_stride;
+    ra.nblk = a.nblk;
+    ra.idx = idx;
+    ra.k = a.k;
+    ra.s = s;
+    ra.mask = row_mask;
+    hipLaunchKernelGGL(gf_locate_checked_resolve_kernel, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, ra);
+    return hipGetLastError();
 }
 
 hipError_t launch_locate_preset(uint32_t* cand, uint64_t nblk, unsigned k, hipStream_t stream) {

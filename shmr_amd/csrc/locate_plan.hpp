@@ -67,5 +67,53 @@ SHMR_LOCATE_HD inline int32_t resolve(uint32_t word, const uint32_t* bitmap, uns
     return found;
 }
 
+// ---- degraded blocks (shmr_ec_locate_checked_batch_dev) --------------------
+// A block with absent shards is compared by its checked plan (gf256.hpp
+// Codec::checked_plan): inputs in_idx[0 .. k), the first k present shards, and
+// one compare row per surplus shard out_idx[0 .. s) in ascending index, rows
+// D = M[surplus] * inv(M[inputs]).  The s surplus shards with the k inputs are
+// an MDS code of their own, so the rule above carries over with D for C:
+//  * surplus shard out_idx[r] damaged: only its row differs -- the word has
+//    exactly its bit;
+//  * input t damaged: every compared row differs (the word is the pattern's row
+//    mask), and s_r == q[r][t] * s_0, q[r][t] = D[r][t] / D[0][t]
+//    (ratio_rows over D; the kernel tests rows 1 .. R-1, R = rows_used(s)).
+// One row cannot tell its own shard from an input: below s = 2 nothing is located.
+
+// The bit of parity shard `shard` (>= k) in a verify / check word.
+SHMR_LOCATE_HD inline unsigned row_bit(unsigned shard, unsigned k) { return shard - k < 31 ? shard - k : 31; }
+
+// The word of a block whose every compared row differs (shmr_ec_checked_rows).
+SHMR_LOCATE_HD inline uint32_t row_mask(const uint16_t* out_idx, unsigned s, unsigned k) {
+    uint32_t mask = 0;
+    for (unsigned r = 0; r < s; ++r) mask |= 1u << row_bit(out_idx[r], k);
+    return mask;
+}
+
+// A degraded block's answer from its check word and candidate bitmap (bit t:
+// plan input t; bits at and above k are ignored): kClean, a shard index in
+// [0, total), or kNone.  s == 0 compares nothing: the word is 0 and the answer
+// kClean, as the checked reconstruct reports such a block.  With every shard
+// present (s = p >= 2, in_idx the identity, out_idx = k .. k+p-1) this is
+// resolve() above, answer for answer.
+SHMR_LOCATE_HD inline int32_t resolve_checked(uint32_t word, const uint32_t* bitmap, unsigned k, unsigned s,
+                                              uint32_t mask, const uint16_t* in_idx, const uint16_t* out_idx) {
+    if (word == 0) return kClean;
+    if (s < 2) return kNone;
+    if ((word & (word - 1)) == 0) {   // one compared row: that surplus shard
+        for (unsigned r = 0; r < s; ++r)
+            if (word == 1u << row_bit(out_idx[r], k)) return int32_t(out_idx[r]);
+        return kNone;
+    }
+    if (word != mask) return kNone;
+    int32_t found = kNone;
+    for (unsigned t = 0; t < k; ++t) {
+        if (!((bitmap[t >> 5] >> (t & 31)) & 1u)) continue;
+        if (found != kNone) return kNone;   // a second candidate
+        found = int32_t(in_idx[t]);
+    }
+    return found;
+}
+
 }  // namespace locate
 }  // namespace shmr

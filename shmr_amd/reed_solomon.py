@@ -560,6 +560,91 @@ class ReedSolomon:
         m = ns.value + nc.value
         return list(in_idx), list(out_idx)[:m], rows[:m * k].reshape(m, k).copy(), int(ns.value)
 
+    def _degraded_batch(self, shards, present, shard_len, what):
+        """The tensor checks of the calls over a degraded batch on the GPU, in
+        ``reconstruct_checked_batch_dev``'s order -> (B, L, present [B, total])."""
+        if shards.dim() != 3:
+            raise TypeError("shards must be a [blocks, total, bytes] tensor")
+        B, t = shards.shape[0], self.total_shard_count()
+        L = shard_len if shard_len is not None else shards.stride(1)
+        self._check_batch_tensor(shards, t, shards.stride(1), L)
+        pr = np.ascontiguousarray(present, dtype=np.uint8)
+        if pr.size != B * t:
+            raise ValueError(f"present must hold {B} x {t} flags")
+        self._check_addressable(shards)
+        if not shards.is_cuda:
+            raise TypeError(f"{what} takes a tensor on the GPU")
+        return B, L, pr.reshape(B, t)
+
+    def locate_checked_batch_dev(self, shards, present: np.ndarray, shard_len: Optional[int] = None,
+                                 data_only: bool = False, rebuild: bool = True, device: Optional[int] = None):
+        """``reconstruct_checked_batch_dev`` that also says which survivor is
+        damaged (``shmr_ec_locate_checked_batch_dev``); same arguments, same
+        bytes written.
+
+        Returns ``(mismatch, located)``, two ``torch.int32`` tensors ``[B]`` on
+        the tensors' device: the words of ``reconstruct_checked_batch_dev``, and
+        per block -1 (``LOCATE_CLEAN``), the index in [0, k + p) of the one
+        present shard whose damage explains the block, or -2 (``LOCATE_NONE``).
+        A block locates only with s >= 2 surplus shards (present shards behind
+        the first k present); with s == 2 damage in two survivors in the same
+        column can pass for damage in a third; inputs are told apart by the
+        first min(s, 4) surplus rows only (shmr_ec.h).  A complete block gets
+        ``locate_batch_dev``'s answer.  Needs 2 <= p <= 32.  Enqueued on torch's
+        current stream; not capturable into a graph."""
+        import torch
+        B, L, pr = self._degraded_batch(shards, present, shard_len, "locate_checked_batch_dev")
+        mismatch = torch.empty(B, dtype=torch.int32, device=shards.device)
+        located = torch.empty(B, dtype=torch.int32, device=shards.device)
+        work = torch.empty(self.locate_work_size(B), dtype=torch.uint8, device=shards.device)
+        dev, stream = self._stream_and_device(shards)
+        dev = dev if device is None else int(device)
+        flags = (self.CHECK_DATA_ONLY if data_only else 0) | (0 if rebuild else self.CHECK_NO_REBUILD)
+        _check(self._L.shmr_ec_locate_checked_batch_dev(
+            self._h, ctypes.c_void_p(shards.data_ptr()), shards.stride(1), shards.stride(0), _ptr(pr), B, L, flags,
+            ctypes.c_void_p(mismatch.data_ptr()), ctypes.c_void_p(located.data_ptr()),
+            ctypes.c_void_p(work.data_ptr()), work.numel(), dev, stream))
+        return mismatch, located
+
+    def reconstruct_repair_batch_dev(self, shards, present: np.ndarray, shard_len: Optional[int] = None,
+                                     device: Optional[int] = None):
+        """The whole repair of a degraded batch (``shmr_ec_reconstruct_repair_batch_dev``),
+        blocking: every absent shard rebuilt and the surplus shards compared in
+        one pass, the damaged survivor located, the absent shards and the located
+        one of each such block rebuilt from the good survivors, the whole batch
+        verified.  A block that is not locatable keeps its present shards byte
+        for byte; its absent slots hold the suspect rebuild.
+
+        Returns ``(located, counts)``: a numpy int32 ``[B]`` as
+        ``locate_checked_batch_dev`` gives it, a repaired block that still
+        differs demoted to -2, and the dict ``{"clean", "repaired",
+        "not_repairable"}``.  Waits on torch's current stream; not capturable."""
+        B, L, pr = self._degraded_batch(shards, present, shard_len, "reconstruct_repair_batch_dev")
+        located = np.zeros(B, dtype=np.int32)
+        counts = (ctypes.c_uint64 * 3)()
+        dev, stream = self._stream_and_device(shards)
+        dev = dev if device is None else int(device)
+        _check(self._L.shmr_ec_reconstruct_repair_batch_dev(
+            self._h, ctypes.c_void_p(shards.data_ptr()), shards.stride(1), shards.stride(0), _ptr(pr), B, L,
+            located.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), counts, dev, stream))
+        return located, dict(zip(("clean", "repaired", "not_repairable"), (int(x) for x in counts)))
+
+    def locate_checked_plan(self, present: Sequence[bool]):
+        """(in_idx, out_idx, ratio_rows, row_mask) of what the degraded locate
+        runs for this pattern: the k inputs, the s surplus shards in ascending
+        index, the ``min(s, 4) - 1`` ratio rows D[r][t] / D[0][t] (none for
+        s < 2: nothing can be located) and ``checked_rows(present)``."""
+        t, k = self.total_shard_count(), self.data_shard_count()
+        pr = np.array([1 if x else 0 for x in present], dtype=np.uint8)
+        in_idx = (ctypes.c_uint16 * k)()
+        out_idx = (ctypes.c_uint16 * t)()
+        rows = np.zeros(3 * k, dtype=np.uint8)
+        n, mask = ctypes.c_uint32(), ctypes.c_uint32()
+        _check(self._L.shmr_ec_locate_checked_plan(self._h, _ptr(pr), len(pr), in_idx, out_idx, _ptr(rows), rows.size,
+                                                   ctypes.byref(n), ctypes.byref(mask)))
+        s = max(int(pr.sum()) - k, 0)
+        return list(in_idx), list(out_idx)[:s], rows[:n.value * k].reshape(n.value, k).copy(), int(mask.value)
+
     def reconstruct_batch_dev_out(self, shards, present: np.ndarray, out, shard_len: Optional[int] = None,
                                   data_only: bool = False, device: Optional[int] = None) -> None:
         """Rebuild the absent shards of every block into a separate compact
