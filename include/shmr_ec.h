@@ -399,6 +399,74 @@ int shmr_ec_reconstruct_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard
                                   size_t block_pitch, const uint8_t* present, size_t nblocks,
                                   size_t shard_len, int data_only, int device, void* stream);
 
+/* ---- ranged reads from device-resident blocks, degraded or whole -------------- *
+ * The read half of shmr_ec_update_batch_dev (VirtualBlock::read): byte ranges of
+ * data shards copied out of resident blocks into one destination buffer.  The
+ * code is column-wise -- column c of an absent shard depends only on column c
+ * of the inputs -- so a range of a lost shard is rebuilt from the same range of
+ * `data` survivors, without rebuilding the shard.  For every request,
+ * d_dst[dst_offset .. dst_offset + len) receives bytes [offset, offset + len) of
+ * data shard `shard` of block `block`: the bytes that
+ * shmr_ec_reconstruct_batch_dev(..., data_only = 1) would leave in that shard
+ * for the block's `present` row.
+ *   - shard present: its stored bytes, a plain copy (traffic 2 * len);
+ *   - shard absent: per column the sum over t of D[shard][t] * input_t[col],
+ *     the inputs the first `data` present shards in index order (the crate's
+ *     rule; parity shards can be inputs, never requests), D the row that
+ *     shmr_ec_reconstruct_plan gives for the pattern (traffic (data + 1) * len).
+ * Read-only over the shards: no shard byte is written, absent slots are never
+ * read, and nothing of d_dst outside the requested ranges is written.
+ * NOT checked: the survivors.  A damaged survivor is rebuilt into the answer
+ * exactly as a plain reconstruct rebuilds it; shmr_ec_reconstruct_checked_batch_dev
+ * and shmr_ec_locate_checked_batch_dev are the calls that look. */
+typedef struct shmr_ec_read {
+    uint32_t block;      /* block index, addressed as in shmr_ec_reconstruct_batch_dev */
+    uint32_t shard;      /* data shard, < data */
+    uint64_t offset;     /* first byte within the shard */
+    uint64_t len;        /* bytes, > 0, offset + len <= shard_len */
+    uint64_t dst_offset; /* where the bytes go in d_dst */
+} shmr_ec_read;
+
+/* Serves nreads requests (HOST array) from nblocks blocks addressed exactly as
+ * shmr_ec_reconstruct_batch_dev, `present` as there (HOST flags, nblocks x
+ * total, one pattern per block; blocks of different patterns share a launch).
+ * d_dst: dst_bytes bytes of DEVICE memory on `device`.  d_dst MUST NOT overlap
+ * the shards (the caller's contract: it is not checked, and the result of an
+ * overlap is undefined).  Any alignment of the base, pitches, offset and
+ * dst_offset is accepted.
+ * Checked in this order, all before any device work: NULL rs
+ * (INVALID_ARGUMENT); nreads == 0 or nblocks == 0 (OK, nothing enqueued);
+ * shard_len == 0 (EMPTY_SHARD); a NULL pointer (INVALID_ARGUMENT); per request
+ * block >= nblocks, shard >= data, len == 0, offset + len > shard_len or
+ * dst_offset + len > dst_bytes (INVALID_ARGUMENT); two requests whose
+ * destination ranges intersect (INVALID_ARGUMENT; two requests may read the
+ * same source bytes); a block with fewer than `data` present shards
+ * (TOO_FEW_SHARDS_PRESENT: every block is checked, as the reconstruct does);
+ * the device.
+ * Stream-ordered, no host readback; after the first call on a device no
+ * blocking call and no allocation of the library's own.  NOT capturable: a
+ * `stream` that is being captured into a graph is refused with
+ * INVALID_ARGUMENT and nothing is enqueued.  One launch per table chunk
+ * (shmr_ec_read_plan), counted under SHMR_EC_DEV_LAUNCHES.
+ * Whole-shard reads belong to shmr_ec_reconstruct_batch_dev_out: measured on
+ * RS(8,3) x 4 MiB x 512 blocks, a whole lost shard per block takes 1.19x the
+ * time of that call (small ranges: 5.2x faster at 4 KiB and 3.7x at 64 KiB
+ * than rebuilding the shards and copying the ranges). */
+int shmr_ec_read_batch_dev(shmr_ec_t* rs, const uint8_t* d_shards, size_t shard_pitch,
+                           size_t block_pitch, const uint8_t* present, size_t nblocks,
+                           size_t shard_len, const shmr_ec_read* reads, size_t nreads,
+                           uint8_t* d_dst, size_t dst_bytes, int device, void* stream);
+
+/* Host only; for tests and tools (as shmr_ec_update_rounds): the checks of
+ * shmr_ec_read_batch_dev on the list and the flags, in its order, then per
+ * request whether it is rebuilt (rebuilt: nreads entries, 0 copy / 1 rebuild,
+ * or NULL), the number of kernel pieces (a request is a byte-granular head, whole
+ * 16-byte chunks and a byte-granular tail) and the number of table chunks the
+ * list uploads in (one launch each). */
+int shmr_ec_read_plan(shmr_ec_t* rs, const uint8_t* present, size_t nblocks, size_t shard_len,
+                      const shmr_ec_read* reads, size_t nreads, size_t dst_bytes,
+                      uint8_t* rebuilt, uint32_t* npieces, uint32_t* nchunks);
+
 /* ---- checked reconstruct: verify the spare shards while rebuilding ----------- *
  * shmr_ec_reconstruct_batch_dev reads the first `data` present shards of a
  * block and never looks at the other present ones; shmr_ec_verify_batch_dev

@@ -73,6 +73,12 @@ SIGNATURES = [
     ("shmr_ec_reconstruct_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_int, ctypes.c_int,
       ctypes.c_void_p]),
+    ("shmr_ec_read_batch_dev", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_void_p, _sz, ctypes.c_void_p, _sz,
+      ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_read_plan", ctypes.c_int,
+     [ctypes.c_void_p, _u8p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _u8p, ctypes.POINTER(ctypes.c_uint32),
+      ctypes.POINTER(ctypes.c_uint32)]),
     ("shmr_ec_reconstruct_checked_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
       ctypes.c_void_p]),
@@ -153,6 +159,12 @@ class Update(ctypes.Structure):
     """shmr_ec_update (include/shmr_ec.h)."""
     _fields_ = [("block", ctypes.c_uint32), ("shard", ctypes.c_uint32), ("offset", ctypes.c_uint64),
                 ("len", ctypes.c_uint64), ("src_offset", ctypes.c_uint64)]
+
+
+class Read(ctypes.Structure):
+    """shmr_ec_read (include/shmr_ec.h)."""
+    _fields_ = [("block", ctypes.c_uint32), ("shard", ctypes.c_uint32), ("offset", ctypes.c_uint64),
+                ("len", ctypes.c_uint64), ("dst_offset", ctypes.c_uint64)]
 
 _libs = {}
 _flavour = "tools" if os.environ.get("SHMR_EC_FLAVOUR") == "tools" else "product"

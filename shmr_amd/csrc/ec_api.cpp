@@ -628,6 +628,17 @@ int batch_dev(size_t nblocks, size_t shard_len, int device, Check&& check, Launc
     return launch();
 }
 
+// The host checks of a read list behind rs, the empty call and shard_len, in the
+// header's order: the pointers, the requests and their destinations (the
+// pieces come out of the same pass), then every block's presence flags.
+int read_checks(const Codec& c, bool pointers, const uint8_t* present, size_t nblocks, size_t shard_len,
+                const shmr_ec_read* reads, size_t nreads, size_t dst_bytes, std::vector<shmr::read::Piece>* pieces) {
+    if (!pointers || !present || !reads ||
+        !shmr::read::plan(reads, nreads, nblocks, c.k(), shard_len, dst_bytes, pieces))
+        return SHMR_EC_INVALID_ARGUMENT;
+    return core::validate_presence(c, present, nblocks);
+}
+
 // Every shard a batch call reads or writes has a buffer: all of an encode, and
 // of a reconstruct all but absent parity under data_only.
 bool needed_shards_given(uint8_t* const* shards, const uint8_t* present, size_t nblocks, unsigned k, unsigned t,
@@ -1023,6 +1034,47 @@ int shmr_ec_reconstruct_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard
             return core::reconstruct_on_device(c, device, d_shards, shard_pitch, block_pitch, present, nblocks, shard_len,
                                                data_only != 0, static_cast<hipStream_t>(stream));
         });
+    });
+}
+
+// ---- ranged reads from device-resident blocks ----------------------------------------
+int shmr_ec_read_batch_dev(shmr_ec_t* rs, const uint8_t* d_shards, size_t shard_pitch, size_t block_pitch,
+                           const uint8_t* present, size_t nblocks, size_t shard_len, const shmr_ec_read* reads,
+                           size_t nreads, uint8_t* d_dst, size_t dst_bytes, int device, void* stream) {
+    return guarded([&]() -> int {
+        if (!rs) return SHMR_EC_INVALID_ARGUMENT;
+        if (nreads == 0) return SHMR_EC_OK;
+        Codec& c = *rs->codec;
+        std::vector<shmr::read::Piece> pieces;
+        auto check = [&] {
+            return read_checks(c, d_shards && d_dst, present, nblocks, shard_len, reads, nreads, dst_bytes, &pieces);
+        };
+        return batch_dev(nblocks, shard_len, device, check, [&] {
+            return core::read_on_device(c, device, d_shards, shard_pitch, block_pitch, present, pieces, d_dst,
+                                        static_cast<hipStream_t>(stream));
+        });
+    });
+}
+
+int shmr_ec_read_plan(shmr_ec_t* rs, const uint8_t* present, size_t nblocks, size_t shard_len,
+                      const shmr_ec_read* reads, size_t nreads, size_t dst_bytes, uint8_t* rebuilt, uint32_t* npieces,
+                      uint32_t* nchunks) {
+    return guarded_light([&]() -> int {
+        if (!rs || !npieces || !nchunks) return SHMR_EC_INVALID_ARGUMENT;
+        *npieces = *nchunks = 0;
+        if (nreads == 0 || nblocks == 0) return SHMR_EC_OK;
+        if (shard_len == 0) return SHMR_EC_EMPTY_SHARD;
+        const Codec& c = *rs->codec;
+        std::vector<shmr::read::Piece> pieces;
+        const int rc = read_checks(c, true, present, nblocks, shard_len, reads, nreads, dst_bytes, &pieces);
+        if (rc) return rc;
+        const size_t t = c.k() + c.p();
+        if (rebuilt)
+            for (size_t i = 0; i < nreads; ++i) rebuilt[i] = present[reads[i].block * t + reads[i].shard] ? 0 : 1;
+        if (pieces.size() > 0xffffffffull) return SHMR_EC_INVALID_ARGUMENT;
+        *npieces = uint32_t(pieces.size());
+        *nchunks = shmr::read::count_chunks(pieces);
+        return SHMR_EC_OK;
     });
 }
 

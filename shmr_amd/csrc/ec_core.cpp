@@ -1292,6 +1292,88 @@ int update_on_device(Codec& c, int dev, const Layout& L, const update::Plan& up,
     return SHMR_EC_OK;
 }
 
+// ===========================================================================
+// Ranged reads.  Every pattern with a requested absent shard gets its
+// data-only reconstruct plan on the device first (its rows are exactly the
+// absent data shards, ascending); then the pieces go out in table chunks, one
+// launch each.  A read has no write hazards: no rounds, no order among chunks.
+// ===========================================================================
+int read_on_device(Codec& c, int dev, const uint8_t* d_shards, uint64_t shard_pitch, uint64_t block_pitch,
+                   const uint8_t* present, const std::vector<read::Piece>& ps, uint8_t* d_dst, hipStream_t stream) {
+    static_assert(read::kSlotBytes == UploadRing::kSlotBytes, "one ring slot per chunk");
+    int rc = refuse_capture(dev, stream);
+    if (rc) return rc;
+    const unsigned k = c.k(), t = k + c.p();
+    // the plan image and plan row of every rebuild piece, per pattern and per block
+    struct Pattern {
+        const uint8_t* dplan = nullptr;
+        std::vector<uint32_t> row_of;   // by data shard
+    };
+    std::map<std::vector<uint8_t>, Pattern> patterns;
+    std::map<uint32_t, const Pattern*> of_block;
+    for (const read::Piece& p : ps) {
+        const uint8_t* pr = present + uint64_t(p.block) * t;
+        if (pr[p.shard] || of_block.count(p.block)) continue;
+        std::vector<uint8_t> key(t);
+        for (unsigned i = 0; i < t; ++i) key[i] = pr[i] ? 1 : 0;
+        auto it = patterns.find(key);
+        if (it == patterns.end()) {
+            const std::shared_ptr<Plan> plan = c.reconstruct_plan(key, true);
+            Pattern pat;
+            rc = plan_on_device(*plan, dev, stream, false, &pat.dplan);
+            if (rc) return rc;
+            pat.row_of.assign(k, 0);
+            for (unsigned r = 0; r < plan->m; ++r) pat.row_of[plan->out_idx[r]] = r;
+            it = patterns.emplace(std::move(key), std::move(pat)).first;
+        }
+        of_block[p.block] = &it->second;
+    }
+    // 16-byte accesses: anywhere where the device serves unaligned ones, else
+    // only where every address of the piece is aligned (its columns are)
+    const bool uvec = unaligned_vector(dev);
+    const bool base16 = aligned16(uintptr_t(d_shards)) && aligned16(shard_pitch) && aligned16(block_pitch);
+    kern::ReadArgs a{};
+    a.shards = d_shards;
+    a.dst = d_dst;
+    a.bpitch = block_pitch;
+    a.spitch = shard_pitch;
+    a.k = k;
+    for (size_t c0 = 0; c0 < ps.size();) {
+        const size_t cnt = read::chunk_pieces(ps, c0);
+        uint32_t tiles = 0;
+        rc = with_table(
+            dev, stream, cnt * sizeof(read::DevPiece),
+            [&](uint8_t* h) {
+                read::DevPiece* dp = reinterpret_cast<read::DevPiece*>(h);
+                for (size_t i = 0; i < cnt; ++i) {
+                    const read::Piece& p = ps[c0 + i];
+                    const bool vec = p.vec && (uvec || (base16 && aligned16(uintptr_t(d_dst) + p.dst)));
+                    uint32_t sf = p.shard, flags = vec ? read::kVecFlag : 0u;
+                    uint64_t plan = 0;
+                    if (!present[uint64_t(p.block) * t + p.shard]) {
+                        const Pattern& pat = *of_block.find(p.block)->second;
+                        sf = pat.row_of[p.shard];
+                        plan = uint64_t(uintptr_t(pat.dplan));
+                        flags |= read::kRebuildFlag;
+                    }
+                    dp[i] = read::DevPiece{p.col, p.dst, plan, p.block, p.len, sf | flags, tiles};
+                    tiles += read::piece_tiles(p.len);
+                }
+            },
+            [&](const uint8_t* d) -> int {
+                a.pieces = reinterpret_cast<const read::DevPiece*>(d);
+                a.npieces = uint32_t(cnt);
+                a.ntiles = tiles;
+                count_device(dev, kDevLaunches);
+                SHMR_HIP_TRY(kern::launch_read(a, stream));
+                return SHMR_EC_OK;
+            });
+        if (rc) return rc;
+        c0 += cnt;
+    }
+    return SHMR_EC_OK;
+}
+
 int validate_presence(const Codec& c, const uint8_t* present, uint64_t nblocks) {
     const unsigned k = c.k(), t = k + c.p();
     for (uint64_t b = 0; b < nblocks; ++b) {

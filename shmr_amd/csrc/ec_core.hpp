@@ -16,6 +16,7 @@
 
 #include "gf256.hpp"
 #include "gf_apply.hpp"
+#include "read_plan.hpp"
 #include "shmr_ec.h"
 #include "update_plan.hpp"
 
@@ -300,6 +301,18 @@ int locate_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
 constexpr size_t kUpdateTablePieces = 256 * 1024 / 32;   // UploadRing::kSlotBytes / sizeof(update::DevPiece)
 int update_on_device(Codec& c, int dev, const Layout& L, const update::Plan& up, const uint8_t* d_src,
                      hipStream_t stream);
+// Ranged reads (shmr_ec_read_batch_dev): the planned pieces `ps`
+// (read_plan.hpp, validated by the caller, as `present` is) of blocks laid out
+// as for reconstruct_on_device below, written to d_dst.  A piece of a present
+// shard is a copy; a piece of an absent one names the device image of its
+// pattern's data-only reconstruct plan (the per-pattern cache, uploaded on
+// `stream` on first use) and its row there.  The piece table travels through
+// the upload ring in the chunks of read::chunk_pieces, one launch behind each;
+// blocks of different patterns share a launch.  Stream-ordered, no blocking
+// call after device init; a stream that is being captured is refused
+// (INVALID_ARGUMENT, nothing enqueued).  Nothing but d_dst is written.
+int read_on_device(Codec& c, int dev, const uint8_t* d_shards, uint64_t shard_pitch, uint64_t block_pitch,
+                   const uint8_t* present, const std::vector<read::Piece>& ps, uint8_t* d_dst, hipStream_t stream);
 // The blocks slots[0 .. n) (ascending, distinct) of a single-plan launch set.
 int launch_slots(Plan& plan, int dev, const Layout& L, const uint64_t* slots, uint64_t n, uint64_t len,
                  hipStream_t stream, OpClass op);

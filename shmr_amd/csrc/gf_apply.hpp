@@ -9,6 +9,9 @@ namespace shmr {
 namespace update {
 struct DevPiece;   // update_plan.hpp
 }
+namespace read {
+struct DevPiece;   // read_plan.hpp
+}
 namespace kern {
 
 constexpr int kThreads = 256;                          // lanes per workgroup (4 waves)
@@ -376,6 +379,26 @@ struct UpdateArgs {
     uint32_t p, npieces, tile_base, ntiles;
 };
 hipError_t launch_update(const UpdateArgs& u, hipStream_t stream);
+
+// The ranged read kernel (gf_read.hip; shmr_ec_read_batch_dev): one launch
+// over pieces [0, npieces) of a piece table (read_plan.hpp DevPiece, device
+// memory, tile0 of the first piece 0).  One workgroup per 4 KiB tile of a
+// piece; ntiles = the tiles of these pieces (< 2^31).  All shards of block b
+// at shards + b * bpitch + i * spitch.  A copy piece loads bytes [col, col +
+// len) of its shard; a rebuild piece (kRebuildFlag) those columns of the k
+// inputs its plan image names (DevPiece::plan: a data-only reconstruct plan
+// image, DevPiece::shard its row).  Stores dst[DevPiece::dst, + len) and
+// nothing else.  A piece without kVecFlag moves byte by byte: the edges, and
+// every piece whose addresses are off 16-byte alignment on a device without
+// unaligned vector access.  Not part of kernel_inventory.
+struct ReadArgs {
+    const uint8_t* shards;
+    uint8_t* dst;
+    const read::DevPiece* pieces;
+    uint64_t bpitch, spitch;
+    uint32_t k, npieces, ntiles;
+};
+hipError_t launch_read(const ReadArgs& r, hipStream_t stream);
 
 // The submission queue's completion mark (submit.cpp): a one-wave kernel on
 // `stream` that stores `seq` to `word` -- pinned host memory, a system-scope

@@ -242,6 +242,13 @@ __device__ __forceinline__ void mac(uint32_t (&acc)[R][4], const u32x4& d, const
     }
 }
 
+// Entry e of a plan image's table array, wave-uniform, through scalar loads
+// (the update and read kernels: one input shard at a time, no LDS).
+__device__ __forceinline__ Tab read_tab(const uint8_t* tabs, uint32_t e) {
+    const cu32* t = as_const<cu32>(tabs) + size_t(e) * 8;
+    return Tab{t[0], t[1], t[2], t[3], t[4]};
+}
+
 // Where a workgroup finds its shard offsets and coefficient tables (LDS).
 struct Ctx {
     const uint64_t* s_in_off;   // k entries

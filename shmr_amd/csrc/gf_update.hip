@@ -48,12 +48,6 @@ namespace {
 
 static_assert(update::kTileBytes == uint32_t(kThreads) * 16, "a tile is one 16-byte chunk per lane");
 
-// Entry e of the plan image's table array, through scalar loads.
-__device__ __forceinline__ Tab read_tab(const uint8_t* tabs, uint32_t e) {
-    const cu32* t = as_const<cu32>(tabs) + size_t(e) * 8;
-    return Tab{t[0], t[1], t[2], t[3], t[4]};
-}
-
 // The lane's n bytes (VEC: n = 16) at d (data), s (new bytes) and par (parity
 // row 0; row r at par + r * spitch).
 template <bool VEC>

@@ -335,27 +335,33 @@ class ReedSolomon:
         """``updates`` -> a contiguous array of ``shmr_ec_update``: a sequence of
         ``(block, shard, offset, length, src_offset)`` or an ``(n, 5)`` integer
         array.  Values the C fields cannot hold are an ``InvalidArgument``."""
-        if isinstance(updates, np.ndarray):
-            if updates.dtype.kind not in "iu":
-                raise TypeError("updates must be an integer array")
-            if updates.size and (updates.ndim != 2 or updates.shape[1] != 5):
-                raise TypeError("updates must be an (n, 5) array")
-            a = updates.reshape(-1, 5)
+        return cls._request_array(updates, cls._UPDATE_DTYPE, "updates", "an update", "src_offset")
+
+    @staticmethod
+    def _request_array(rows, dtype, plural: str, one: str, last: str) -> np.ndarray:
+        """The list conversion of ``_update_array`` and ``_read_array``: five
+        integers per entry, two 32-bit and three 64-bit fields of ``dtype``."""
+        if isinstance(rows, np.ndarray):
+            if rows.dtype.kind not in "iu":
+                raise TypeError(f"{plural} must be an integer array")
+            if rows.size and (rows.ndim != 2 or rows.shape[1] != 5):
+                raise TypeError(f"{plural} must be an (n, 5) array")
+            a = rows.reshape(-1, 5)
             if a.dtype.kind == "i" and (a < 0).any():
                 raise Error(-100)                                # InvalidArgument
             a = a.astype(np.uint64)
             if (a[:, :2] >> np.uint64(32)).any():
                 raise Error(-100)
-            out = np.zeros(len(a), dtype=cls._UPDATE_DTYPE)
-            for i, name in enumerate(cls._UPDATE_DTYPE.names):
+            out = np.zeros(len(a), dtype=dtype)
+            for i, name in enumerate(dtype.names):
                 out[name] = a[:, i]
             return out
         else:
-            rows = [tuple(row) for row in updates]
-        out = np.zeros(len(rows), dtype=cls._UPDATE_DTYPE)
+            rows = [tuple(row) for row in rows]
+        out = np.zeros(len(rows), dtype=dtype)
         for i, row in enumerate(rows):
             if len(row) != 5 or not all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in row):
-                raise TypeError("an update is five integers: (block, shard, offset, length, src_offset)")
+                raise TypeError(f"{one} is five integers: (block, shard, offset, length, {last})")
             b, s, off, n, src = (int(x) for x in row)
             if not (0 <= b < 1 << 32 and 0 <= s < 1 << 32 and all(0 <= x < 1 << 64 for x in (off, n, src))):
                 raise Error(-100)                                # InvalidArgument
@@ -408,6 +414,92 @@ class ReedSolomon:
         """``update_batch_dev`` of one ``[B, k + p, pitch]`` tensor, as ``verify_shards_dev``."""
         data, parity = self._split_shards(shards)
         self.update_batch_dev(data, parity, updates, src, shard_len=shard_len, device=device)
+
+    # -- ranged reads from device-resident blocks -----------------------------------
+    _READ_DTYPE = np.dtype([("block", "<u4"), ("shard", "<u4"), ("offset", "<u8"), ("len", "<u8"),
+                            ("dst_offset", "<u8")], align=True)
+
+    @classmethod
+    def _read_array(cls, reads) -> np.ndarray:
+        """``reads`` -> a contiguous array of ``shmr_ec_read``: a sequence of
+        ``(block, shard, offset, length, dst_offset)`` or an ``(n, 5)`` integer
+        array, converted as ``_update_array`` converts updates."""
+        return cls._request_array(reads, cls._READ_DTYPE, "reads", "a read", "dst_offset")
+
+    @staticmethod
+    def block_range_reads(block: int, pos: int, length: int, shard_len: int, dst_offset: int = 0) -> list:
+        """The requests of a ``VirtualBlock::read(pos, length)``: bytes [pos, pos +
+        length) of the block's payload, where data shard i holds payload bytes
+        [i * shard_len, (i + 1) * shard_len), split at shard boundaries into
+        ``(block, shard, offset, length, dst_offset)`` tuples whose destinations
+        follow one another from ``dst_offset``.  Pure: the caller keeps the
+        range inside the payload (shard < data is checked by the read call)."""
+        block, pos, length, shard_len, dst_offset = (int(x) for x in (block, pos, length, shard_len, dst_offset))
+        if block < 0 or pos < 0 or length < 0 or shard_len <= 0 or dst_offset < 0:
+            raise ValueError("block, pos, length and dst_offset must be >= 0 and shard_len > 0")
+        out = []
+        while length:
+            shard, off = divmod(pos, shard_len)
+            n = min(length, shard_len - off)
+            out.append((block, shard, off, n, dst_offset))
+            pos, dst_offset, length = pos + n, dst_offset + n, length - n
+        return out
+
+    def read_plan(self, present: np.ndarray, reads, shard_len: int, dst_bytes: int):
+        """``shmr_ec_read_plan`` (host only): the checks ``read_batch_dev`` makes on
+        the list and on ``present`` (host flags ``[B, total]``), then ``(rebuilt,
+        npieces, nchunks)``: a numpy uint8 array with 1 for every request that
+        is rebuilt (its shard is absent) and 0 for a copy, the number of kernel
+        pieces, and the number of table chunks (launches) of the list."""
+        t = self.total_shard_count()
+        pr = np.ascontiguousarray(present, dtype=np.uint8)
+        if pr.size % t:
+            raise ValueError(f"present must hold {t} flags per block")
+        ra = self._read_array(reads)
+        rebuilt = np.zeros(len(ra), dtype=np.uint8)
+        npieces, nchunks = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(self._L.shmr_ec_read_plan(self._h, _ptr(pr), pr.size // t, shard_len, ctypes.c_void_p(ra.ctypes.data),
+                                         len(ra), dst_bytes, _ptr(rebuilt), ctypes.byref(npieces),
+                                         ctypes.byref(nchunks)))
+        return rebuilt, int(npieces.value), int(nchunks.value)
+
+    def read_batch_dev(self, shards, present: np.ndarray, reads, dst, shard_len: Optional[int] = None,
+                       device: Optional[int] = None) -> None:
+        """Reads byte ranges of data shards out of device-resident blocks, lost
+        shards included (``shmr_ec_read_batch_dev``): shards and present as
+        ``reconstruct_batch_dev`` takes them (same checks in the same order);
+        ``dst`` a 1-D uint8 tensor on the same GPU, which must not overlap
+        shards.  For every ``(block, shard, offset, length, dst_offset)`` of
+        ``reads``, ``dst[dst_offset : dst_offset + length]`` receives bytes
+        [offset, offset + length) of that data shard: copied if the shard is
+        present, else rebuilt from those columns of the first k present shards
+        -- what ``reconstruct_batch_dev(data_only=True)`` would leave there.
+        No shard is written and nothing else of ``dst``.  Survivors are not
+        checked for damage (``reconstruct_checked_batch_dev`` does that).
+        Enqueued on torch's current stream; not for graph capture (the native
+        call refuses a stream that is being captured)."""
+        import torch
+        if shards.dim() != 3:
+            raise TypeError("shards must be a [blocks, total, bytes] tensor")
+        B, t = shards.shape[0], self.total_shard_count()
+        L = shard_len if shard_len is not None else shards.stride(1)
+        self._check_batch_tensor(shards, t, shards.stride(1), L)
+        pr = np.ascontiguousarray(present, dtype=np.uint8)
+        if pr.size != B * t:
+            raise ValueError(f"present must hold {B} x {t} flags")
+        pr = pr.reshape(B, t)
+        self._check_addressable(shards)
+        if (not isinstance(dst, torch.Tensor) or dst.dtype != torch.uint8 or dst.dim() != 1
+                or (dst.numel() > 1 and dst.stride(0) != 1)):
+            raise TypeError("dst must be a 1-D contiguous torch.uint8 tensor")
+        if dst.device != shards.device:
+            raise TypeError(f"dst must be on {shards.device}")
+        ra = self._read_array(reads)
+        dev, stream = self._stream_and_device(shards)
+        dev = dev if device is None else int(device)
+        _check(self._L.shmr_ec_read_batch_dev(self._h, ctypes.c_void_p(shards.data_ptr()), shards.stride(1),
+                                              shards.stride(0), _ptr(pr), B, L, ctypes.c_void_p(ra.ctypes.data),
+                                              len(ra), ctypes.c_void_p(dst.data_ptr()), dst.numel(), dev, stream))
 
     # -- device-resident batches (torch tensors on the GPU) ------------------------
     @staticmethod
