@@ -66,6 +66,28 @@ struct SlabEntry {
 };
 std::mutex g_slab_mu;
 std::map<uintptr_t, SlabEntry> g_slabs;
+
+// The crate's checks of one presence pattern for the host-only *_plan exports.
+int check_pattern(const shmr_ec_t* rs, const uint8_t* present, size_t nshards) {
+    const unsigned k = rs->codec->k(), t = k + rs->codec->p();
+    if (nshards < t) return SHMR_EC_TOO_FEW_SHARDS;
+    if (nshards > t) return SHMR_EC_TOO_MANY_SHARDS;
+    unsigned np = 0;
+    for (unsigned i = 0; i < t; ++i) np += present[i] ? 1 : 0;
+    return np < k ? SHMR_EC_TOO_FEW_SHARDS_PRESENT : SHMR_EC_OK;
+}
+
+// A plan's k inputs, its first n_out outputs and the n_rows rows of `rows`
+// (null: none) to the caller of a *_plan export; rows_len: what out_rows holds.
+int copy_plan_out(const Plan& plan, unsigned n_out, const Plan* rows, uint16_t* in_idx, uint16_t* out_idx,
+                  uint8_t* out_rows, size_t rows_len) {
+    const size_t k = plan.k, n_rows = rows ? rows->m : 0;
+    if (rows_len < n_rows * k) return SHMR_EC_INVALID_ARGUMENT;
+    std::memcpy(in_idx, plan.in_idx.data(), 2 * k);
+    if (n_out) std::memcpy(out_idx, plan.out_idx.data(), 2 * size_t(n_out));
+    if (n_rows) std::memcpy(out_rows, rows->rows.d.data(), n_rows * k);
+    return SHMR_EC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -160,22 +182,16 @@ int shmr_ec_reconstruct_plan(shmr_ec_t* rs, const uint8_t* present, size_t nshar
                              uint32_t* n_out) {
     return guarded([&]() -> int {
         if (!rs || !present || !in_idx || !out_idx || !out_rows || !n_out) return SHMR_EC_INVALID_ARGUMENT;
-        const unsigned k = rs->codec->k(), t = k + rs->codec->p();
-        if (nshards < t) return SHMR_EC_TOO_FEW_SHARDS;
-        if (nshards > t) return SHMR_EC_TOO_MANY_SHARDS;
-        unsigned np = 0;
-        for (unsigned i = 0; i < t; ++i) np += present[i] ? 1 : 0;
-        if (np == t) {
+        int rc = check_pattern(rs, present, nshards);
+        if (rc) return rc;
+        const unsigned t = rs->codec->k() + rs->codec->p();
+        if (std::all_of(present, present + t, [](uint8_t x) { return x != 0; })) {   // crate: all present -> Ok(())
             *n_out = 0;
             return SHMR_EC_OK;
         }
-        if (np < k) return SHMR_EC_TOO_FEW_SHARDS_PRESENT;
         std::vector<uint8_t> pr(present, present + t);
         auto plan = rs->codec->reconstruct_plan(pr, data_only != 0);
-        if (out_rows_len < size_t(plan->m) * k) return SHMR_EC_INVALID_ARGUMENT;
-        std::memcpy(in_idx, plan->in_idx.data(), 2 * size_t(k));
-        std::memcpy(out_idx, plan->out_idx.data(), 2 * size_t(plan->m));
-        std::memcpy(out_rows, plan->rows.d.data(), size_t(plan->m) * k);
+        if ((rc = copy_plan_out(*plan, plan->m, plan.get(), in_idx, out_idx, out_rows, out_rows_len))) return rc;
         *n_out = plan->m;
         return SHMR_EC_OK;
     });
@@ -639,6 +655,72 @@ int read_checks(const Codec& c, bool pointers, const uint8_t* present, size_t nb
     return core::validate_presence(c, present, nblocks);
 }
 
+// The flags of the checked calls that this build knows.
+constexpr int kCheckFlags = SHMR_EC_CHECK_DATA_ONLY | SHMR_EC_CHECK_NO_REBUILD;
+
+// Locate, rebuild, verify again (scrub, reconstruct-repair), blocking.
+// check(): the call's own pointers and flags, as batch_dev takes it.
+// locate(d_words, d_located, d_cand) enqueues the call's locate into pooled
+// scratch; rebuild(hit, located) rebuilds the located blocks `hit` and returns
+// its status and the layout of the closing verify.  counts (clean, repaired,
+// not repairable) are written only by a call that is accepted; a rebuilt block
+// that still differs is demoted to SHMR_EC_LOCATE_NONE.
+template <class Check, class Locate, class Rebuild>
+int locate_rebuild_verify(shmr_ec_t* rs, size_t nblocks, size_t shard_len, int32_t* located_host, uint64_t* counts,
+                          int device, hipStream_t stream, Check&& check, Locate&& locate, Rebuild&& rebuild) {
+    if (!rs || !counts || !rs->codec->locate_plan()) return SHMR_EC_INVALID_ARGUMENT;
+    // (an empty batch is accepted)
+    if (nblocks == 0) counts[0] = counts[1] = counts[2] = 0;
+    Codec& c = *rs->codec;
+    return batch_dev(nblocks, shard_len, device, check, [&]() -> int {
+        int rc = core::refuse_capture(device, stream);   // it waits for its own results
+        if (rc) return rc;
+        counts[0] = counts[1] = counts[2] = 0;
+        // pooled scratch (grown without a free): the words, the answers, the candidate bitmaps
+        const size_t words_bytes = size_t(core::round_up(nblocks * sizeof(uint32_t), 256));
+        core::StagingLease lease;
+        lease.s = core::StagingPool::get().acquire(device, 2 * words_bytes + core::locate_work_bytes(c, nblocks), &rc);
+        if (!lease.s) return rc;
+        uint32_t* d_words = reinterpret_cast<uint32_t*>(lease.s->dbuf);
+        int32_t* d_located = reinterpret_cast<int32_t*>(lease.s->dbuf + words_bytes);
+        uint32_t* d_cand = reinterpret_cast<uint32_t*>(lease.s->dbuf + 2 * words_bytes);
+        // (a failure below still waits: the scratch goes back to the pool idle)
+        auto fetch = [&](void* dst, const void* src) -> int {
+            const hipError_t e = hipMemcpyAsync(dst, src, nblocks * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+            const hipError_t w = core::sync_stream(stream);
+            return e == hipSuccess && w == hipSuccess ? SHMR_EC_OK : SHMR_EC_DEVICE_ERROR;
+        };
+        std::vector<int32_t> own;
+        int32_t* located = located_host;
+        if (!located) {
+            own.resize(nblocks);
+            located = own.data();
+        }
+        rc = locate(d_words, d_located, d_cand);
+        const int frc = fetch(located, d_located);
+        if (rc || frc) return rc ? rc : frc;
+        std::vector<size_t> hit;
+        for (size_t b = 0; b < nblocks; ++b) {
+            if (located[b] >= 0) hit.push_back(b);
+            else ++counts[located[b] == SHMR_EC_LOCATE_CLEAN ? 0 : 2];
+        }
+        if (hit.empty()) return SHMR_EC_OK;
+        const std::pair<int, core::Layout> rebuilt = rebuild(hit, located);
+        rc = rebuilt.first;
+        // the closing verify (every slot has been written by now): damage
+        // beyond what locate looked at shows here
+        if (rc == SHMR_EC_OK) rc = core::verify_on_device(c, device, rebuilt.second, nblocks, shard_len, d_words, stream);
+        std::vector<uint32_t> words(nblocks);
+        const int wrc = fetch(words.data(), d_words);
+        if (rc || wrc) return rc ? rc : wrc;
+        for (size_t b : hit) {
+            if (words[b] != 0) located[b] = SHMR_EC_LOCATE_NONE;
+            ++counts[words[b] != 0 ? 2 : 1];
+        }
+        return SHMR_EC_OK;
+    });
+}
+
 // Every shard a batch call reads or writes has a buffer: all of an encode, and
 // of a reconstruct all but absent parity under data_only.
 bool needed_shards_given(uint8_t* const* shards, const uint8_t* present, size_t nblocks, unsigned k, unsigned t,
@@ -916,71 +998,35 @@ int shmr_ec_scrub_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pi
                             uint8_t* d_parity, size_t parity_shard_pitch, size_t parity_block_pitch, size_t nblocks,
                             size_t shard_len, int32_t* located_host, uint64_t* counts, int device, void* stream_) {
     return guarded([&]() -> int {
-        if (!rs || !counts || !rs->codec->locate_plan()) return SHMR_EC_INVALID_ARGUMENT;
-        // (counts are written only by a call that is accepted: an empty batch, or below)
-        if (nblocks == 0) counts[0] = counts[1] = counts[2] = 0;
-        Codec& c = *rs->codec;
         hipStream_t stream = static_cast<hipStream_t>(stream_);
-        return batch_dev(nblocks, shard_len, device, [&] { return arg_ok(d_data && d_parity); }, [&]() -> int {
-            int rc = core::refuse_capture(device, stream);   // it waits for its own results
-            if (rc) return rc;
-            counts[0] = counts[1] = counts[2] = 0;
-            const unsigned k = c.k(), t = k + c.p();
-            const core::Layout L = batch_layout(c, d_data, data_shard_pitch, data_block_pitch, d_parity,
-                                                parity_shard_pitch, parity_block_pitch);
-            // pooled scratch (grown without a free): the words, the answers, the candidate bitmaps
-            const size_t words_bytes = size_t(core::round_up(nblocks * sizeof(uint32_t), 256));
-            core::StagingLease lease;
-            lease.s = core::StagingPool::get().acquire(device, 2 * words_bytes + core::locate_work_bytes(c, nblocks), &rc);
-            if (!lease.s) return rc;
-            uint32_t* d_words = reinterpret_cast<uint32_t*>(lease.s->dbuf);
-            int32_t* d_located = reinterpret_cast<int32_t*>(lease.s->dbuf + words_bytes);
-            uint32_t* d_cand = reinterpret_cast<uint32_t*>(lease.s->dbuf + 2 * words_bytes);
-            // (a failure below still waits: the scratch goes back to the pool idle)
-            auto fetch = [&](void* dst, const void* src) -> int {
-                const hipError_t e = hipMemcpyAsync(dst, src, nblocks * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-                const hipError_t w = core::sync_stream(stream);
-                return e == hipSuccess && w == hipSuccess ? SHMR_EC_OK : SHMR_EC_DEVICE_ERROR;
-            };
-            std::vector<int32_t> own;
-            int32_t* located = located_host;
-            if (!located) {
-                own.resize(nblocks);
-                located = own.data();
-            }
-            rc = core::locate_on_device(c, device, L, nblocks, shard_len, d_words, d_located, d_cand, stream);
-            const int frc = fetch(located, d_located);
-            if (rc || frc) return rc ? rc : frc;
+        auto layout = [&] {
+            return batch_layout(*rs->codec, d_data, data_shard_pitch, data_block_pitch, d_parity, parity_shard_pitch,
+                                parity_block_pitch);
+        };
+        return locate_rebuild_verify(
+            rs, nblocks, shard_len, located_host, counts, device, stream, [&] { return arg_ok(d_data && d_parity); },
+            [&](uint32_t* d_words, int32_t* d_located, uint32_t* d_cand) {
+                return core::locate_on_device(*rs->codec, device, layout(), nblocks, shard_len, d_words, d_located,
+                                              d_cand, stream);
+            },
             // the located shard of every such block, rebuilt from the block's other shards
-            std::vector<size_t> hit;
-            for (size_t b = 0; b < nblocks; ++b) {
-                if (located[b] >= 0) hit.push_back(b);
-                else ++counts[located[b] == SHMR_EC_LOCATE_CLEAN ? 0 : 2];
-            }
-            if (hit.empty()) return SHMR_EC_OK;
-            std::vector<uint64_t> tab(hit.size() * t);
-            std::vector<uint8_t> present(hit.size() * t, 1);
-            for (size_t i = 0; i < hit.size(); ++i) {
-                const size_t b = hit[i];
-                for (unsigned s = 0; s < t; ++s)
-                    tab[i * t + s] = s < k ? uint64_t(uintptr_t(d_data + b * data_block_pitch + s * data_shard_pitch))
-                                           : uint64_t(uintptr_t(d_parity + b * parity_block_pitch +
-                                                                (s - k) * parity_shard_pitch));
-                present[i * t + size_t(located[b])] = 0;
-            }
-            rc = core::ptrs_launch(c, tab.data(), present.data(), hit.size(), shard_len, false, device, stream,
-                                   core::kDecode, false, false);
-            // the closing verify: damage beyond what locate looked at shows here
-            if (rc == SHMR_EC_OK) rc = core::verify_on_device(c, device, L, nblocks, shard_len, d_words, stream);
-            std::vector<uint32_t> words(nblocks);
-            const int wrc = fetch(words.data(), d_words);
-            if (rc || wrc) return rc ? rc : wrc;
-            for (size_t b : hit) {
-                if (words[b] != 0) located[b] = SHMR_EC_LOCATE_NONE;
-                ++counts[words[b] != 0 ? 2 : 1];
-            }
-            return SHMR_EC_OK;
-        });
+            [&](const std::vector<size_t>& hit, const int32_t* located) {
+                Codec& c = *rs->codec;
+                const unsigned k = c.k(), t = k + c.p();
+                std::vector<uint64_t> tab(hit.size() * t);
+                std::vector<uint8_t> present(hit.size() * t, 1);
+                for (size_t i = 0; i < hit.size(); ++i) {
+                    const size_t b = hit[i];
+                    for (unsigned s = 0; s < t; ++s)
+                        tab[i * t + s] = s < k ? uint64_t(uintptr_t(d_data + b * data_block_pitch + s * data_shard_pitch))
+                                               : uint64_t(uintptr_t(d_parity + b * parity_block_pitch +
+                                                                    (s - k) * parity_shard_pitch));
+                    present[i * t + size_t(located[b])] = 0;
+                }
+                return std::make_pair(core::ptrs_launch(c, tab.data(), present.data(), hit.size(), shard_len, false,
+                                                        device, stream, core::kDecode, false, false),
+                                      layout());
+            });
     });
 }
 
@@ -1085,8 +1131,7 @@ int shmr_ec_reconstruct_checked_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size
     return guarded([&]() -> int {
         if (!rs) return SHMR_EC_INVALID_ARGUMENT;
         Codec& c = *rs->codec;
-        const int known = SHMR_EC_CHECK_DATA_ONLY | SHMR_EC_CHECK_NO_REBUILD;
-        const bool given = d_shards && present && words_given(d_mismatch) && (flags & ~known) == 0;
+        const bool given = d_shards && present && words_given(d_mismatch) && (flags & ~kCheckFlags) == 0;
         // (no launch on a bad batch)
         auto check = [&] { return given ? core::validate_presence(c, present, nblocks) : arg_ok(false); };
         return batch_dev(nblocks, shard_len, device, check, [&] {
@@ -1096,16 +1141,6 @@ int shmr_ec_reconstruct_checked_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size
                                            static_cast<hipStream_t>(stream));
         });
     });
-}
-
-// The crate's checks of one presence pattern for the host-only exports below.
-static int check_pattern(const shmr_ec_t* rs, const uint8_t* present, size_t nshards) {
-    const unsigned k = rs->codec->k(), t = k + rs->codec->p();
-    if (nshards < t) return SHMR_EC_TOO_FEW_SHARDS;
-    if (nshards > t) return SHMR_EC_TOO_MANY_SHARDS;
-    unsigned np = 0;
-    for (unsigned i = 0; i < t; ++i) np += present[i] ? 1 : 0;
-    return np < k ? SHMR_EC_TOO_FEW_SHARDS_PRESENT : SHMR_EC_OK;
 }
 
 int shmr_ec_checked_rows(const shmr_ec_t* rs, const uint8_t* present, size_t nshards, uint32_t* rows) {
@@ -1131,19 +1166,14 @@ int shmr_ec_checked_plan(shmr_ec_t* rs, const uint8_t* present, size_t nshards, 
                          uint32_t* n_check) {
     return guarded_light([&]() -> int {
         if (!rs || !present || !in_idx || !out_idx || !out_rows || !n_store || !n_check) return SHMR_EC_INVALID_ARGUMENT;
-        if ((flags & ~(SHMR_EC_CHECK_DATA_ONLY | SHMR_EC_CHECK_NO_REBUILD)) != 0) return SHMR_EC_INVALID_ARGUMENT;
-        const int rc = check_pattern(rs, present, nshards);
+        if ((flags & ~kCheckFlags) != 0) return SHMR_EC_INVALID_ARGUMENT;
+        int rc = check_pattern(rs, present, nshards);
         if (rc) return rc;
-        const unsigned k = rs->codec->k(), t = k + rs->codec->p();
-        std::vector<uint8_t> pr(present, present + t);
+        std::vector<uint8_t> pr(present, present + rs->codec->k() + rs->codec->p());
         auto plan = rs->codec->checked_plan(pr, (flags & SHMR_EC_CHECK_DATA_ONLY) != 0,
                                             (flags & SHMR_EC_CHECK_NO_REBUILD) != 0);
-        if (out_rows_len < size_t(plan->m) * k) return SHMR_EC_INVALID_ARGUMENT;
-        std::memcpy(in_idx, plan->in_idx.data(), 2 * size_t(k));
-        if (plan->m) {   // (exactly k present and nothing rebuilt: an empty plan)
-            std::memcpy(out_idx, plan->out_idx.data(), 2 * size_t(plan->m));
-            std::memcpy(out_rows, plan->rows.d.data(), size_t(plan->m) * k);
-        }
+        // (exactly k present and nothing rebuilt: an empty plan)
+        if ((rc = copy_plan_out(*plan, plan->m, plan.get(), in_idx, out_idx, out_rows, out_rows_len))) return rc;
         *n_store = plan->m - plan->n_check;
         *n_check = plan->n_check;
         return SHMR_EC_OK;
@@ -1156,21 +1186,17 @@ int shmr_ec_locate_checked_plan(shmr_ec_t* rs, const uint8_t* present, size_t ns
                                 uint32_t* row_mask) {
     return guarded_light([&]() -> int {
         if (!rs || !present || !in_idx || !out_idx || !ratio_rows || !n_rows || !row_mask) return SHMR_EC_INVALID_ARGUMENT;
-        const int rc = check_pattern(rs, present, nshards);
+        int rc = check_pattern(rs, present, nshards);
         if (rc) return rc;
-        const unsigned k = rs->codec->k(), t = k + rs->codec->p();
-        std::vector<uint8_t> pr(present, present + t);
+        const unsigned k = rs->codec->k();
+        std::vector<uint8_t> pr(present, present + k + rs->codec->p());
         const auto cp = rs->codec->checked_plan(pr, false, true);
         const unsigned s = cp->n_check;
         bool singular = false;
         const auto lp = rs->codec->locate_checked_plan(pr, &singular);
         if (singular) return SHMR_EC_INVALID_ARGUMENT;
-        const unsigned rows = lp ? lp->m : 0;
-        if (ratio_rows_len < size_t(rows) * k) return SHMR_EC_INVALID_ARGUMENT;
-        std::memcpy(in_idx, cp->in_idx.data(), 2 * size_t(k));
-        if (s) std::memcpy(out_idx, cp->out_idx.data(), 2 * size_t(s));
-        if (rows) std::memcpy(ratio_rows, lp->rows.d.data(), size_t(rows) * k);
-        *n_rows = rows;
+        if ((rc = copy_plan_out(*cp, s, lp.get(), in_idx, out_idx, ratio_rows, ratio_rows_len))) return rc;
+        *n_rows = lp ? lp->m : 0;
         *row_mask = shmr::locate::row_mask(cp->out_idx.data(), s, k);
         return SHMR_EC_OK;
     });
@@ -1183,10 +1209,9 @@ int shmr_ec_locate_checked_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t sh
     return guarded([&]() -> int {
         if (!rs || !rs->codec->locate_plan()) return SHMR_EC_INVALID_ARGUMENT;
         Codec& c = *rs->codec;
-        const int known = SHMR_EC_CHECK_DATA_ONLY | SHMR_EC_CHECK_NO_REBUILD;
         const bool given = d_shards && present && words_given(d_mismatch) && words_given(d_located) &&
                            words_given(d_work) && work_bytes >= core::locate_work_bytes(c, nblocks) &&
-                           (flags & ~known) == 0;
+                           (flags & ~kCheckFlags) == 0;
         // (no launch on a bad batch)
         auto check = [&] { return given ? core::validate_presence(c, present, nblocks) : arg_ok(false); };
         return batch_dev(nblocks, shard_len, device, check, [&] {
@@ -1202,76 +1227,34 @@ int shmr_ec_reconstruct_repair_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_
                                          const uint8_t* present, size_t nblocks, size_t shard_len,
                                          int32_t* located_host, uint64_t* counts, int device, void* stream_) {
     return guarded([&]() -> int {
-        if (!rs || !counts || !rs->codec->locate_plan()) return SHMR_EC_INVALID_ARGUMENT;
-        // (counts are written only by a call that is accepted: an empty batch, or below)
-        if (nblocks == 0) counts[0] = counts[1] = counts[2] = 0;
-        Codec& c = *rs->codec;
         hipStream_t stream = static_cast<hipStream_t>(stream_);
-        // (no launch on a bad batch)
-        auto check = [&] { return d_shards && present ? core::validate_presence(c, present, nblocks) : arg_ok(false); };
-        return batch_dev(nblocks, shard_len, device, check, [&]() -> int {
-            int rc = core::refuse_capture(device, stream);   // it waits for its own results
-            if (rc) return rc;
-            counts[0] = counts[1] = counts[2] = 0;
-            const unsigned k = c.k(), t = k + c.p();
-            // pooled scratch (grown without a free): the words, the answers, the candidate bitmaps
-            const size_t words_bytes = size_t(core::round_up(nblocks * sizeof(uint32_t), 256));
-            core::StagingLease lease;
-            lease.s = core::StagingPool::get().acquire(device, 2 * words_bytes + core::locate_work_bytes(c, nblocks), &rc);
-            if (!lease.s) return rc;
-            uint32_t* d_words = reinterpret_cast<uint32_t*>(lease.s->dbuf);
-            int32_t* d_located = reinterpret_cast<int32_t*>(lease.s->dbuf + words_bytes);
-            uint32_t* d_cand = reinterpret_cast<uint32_t*>(lease.s->dbuf + 2 * words_bytes);
-            // (a failure below still waits: the scratch goes back to the pool idle)
-            auto fetch = [&](void* dst, const void* src) -> int {
-                const hipError_t e = hipMemcpyAsync(dst, src, nblocks * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-                const hipError_t w = core::sync_stream(stream);
-                return e == hipSuccess && w == hipSuccess ? SHMR_EC_OK : SHMR_EC_DEVICE_ERROR;
-            };
-            std::vector<int32_t> own;
-            int32_t* located = located_host;
-            if (!located) {
-                own.resize(nblocks);
-                located = own.data();
-            }
+        return locate_rebuild_verify(
+            rs, nblocks, shard_len, located_host, counts, device, stream,
+            // (no launch on a bad batch)
+            [&] { return d_shards && present ? core::validate_presence(*rs->codec, present, nblocks) : arg_ok(false); },
             // every absent shard rebuilt, every surplus shard compared, one pass
-            rc = core::locate_checked_on_device(c, device, d_shards, shard_pitch, block_pitch, present, nblocks,
-                                                shard_len, false, false, d_words, d_located, d_cand, stream);
-            const int frc = fetch(located, d_located);
-            if (rc || frc) return rc ? rc : frc;
+            [&](uint32_t* d_words, int32_t* d_located, uint32_t* d_cand) {
+                return core::locate_checked_on_device(*rs->codec, device, d_shards, shard_pitch, block_pitch, present,
+                                                      nblocks, shard_len, false, false, d_words, d_located, d_cand,
+                                                      stream);
+            },
             // a located block: its absent shards (rebuilt above from a damaged input,
             // where it was one) and the located shard, from the good survivors.
             // Every other block counts as complete here: nothing to rebuild.
-            std::vector<size_t> hit;
-            std::vector<uint8_t> pr(nblocks * t, 1);
-            for (size_t b = 0; b < nblocks; ++b) {
-                if (located[b] < 0) {
-                    ++counts[located[b] == SHMR_EC_LOCATE_CLEAN ? 0 : 2];
-                    continue;
+            [&](const std::vector<size_t>& hit, const int32_t* located) {
+                Codec& c = *rs->codec;
+                const unsigned k = c.k(), t = k + c.p();
+                std::vector<uint8_t> pr(nblocks * t, 1);
+                for (size_t b : hit) {
+                    for (unsigned i = 0; i < t; ++i) pr[b * t + i] = present[b * t + i] ? 1 : 0;
+                    pr[b * t + size_t(located[b])] = 0;
                 }
-                hit.push_back(b);
-                for (unsigned i = 0; i < t; ++i) pr[b * t + i] = present[b * t + i] ? 1 : 0;
-                pr[b * t + size_t(located[b])] = 0;
-            }
-            if (hit.empty()) return SHMR_EC_OK;
-            rc = core::reconstruct_on_device(c, device, d_shards, shard_pitch, block_pitch, pr.data(), nblocks, shard_len,
-                                             false, stream);
-            // the closing verify (every slot has been written by now): damage
-            // beyond what locate looked at shows here
-            if (rc == SHMR_EC_OK) {
-                const core::Layout L = batch_layout(c, d_shards, shard_pitch, block_pitch, d_shards + k * shard_pitch,
-                                                    shard_pitch, block_pitch);
-                rc = core::verify_on_device(c, device, L, nblocks, shard_len, d_words, stream);
-            }
-            std::vector<uint32_t> words(nblocks);
-            const int wrc = fetch(words.data(), d_words);
-            if (rc || wrc) return rc ? rc : wrc;
-            for (size_t b : hit) {
-                if (words[b] != 0) located[b] = SHMR_EC_LOCATE_NONE;
-                ++counts[words[b] != 0 ? 2 : 1];
-            }
-            return SHMR_EC_OK;
-        });
+                return std::make_pair(
+                    core::reconstruct_on_device(c, device, d_shards, shard_pitch, block_pitch, pr.data(), nblocks,
+                                                shard_len, false, stream),
+                    batch_layout(c, d_shards, shard_pitch, block_pitch, d_shards + k * shard_pitch, shard_pitch,
+                                 block_pitch));
+            });
     });
 }
 

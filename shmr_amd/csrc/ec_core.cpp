@@ -992,6 +992,24 @@ int with_block_lists(int dev, hipStream_t stream, const uint64_t* blocks, uint64
     }
     return SHMR_EC_OK;
 }
+
+// launch() over `blocks`, named in `a`: an arithmetic sequence by first and
+// stride, any other through uploaded block lists, once per chunk.
+template <class Launch>
+int over_blocks(int dev, hipStream_t stream, kern::ApplyArgs& a, const std::vector<uint64_t>& blocks, Launch launch) {
+    uint64_t stride = 1;
+    if (arith_stride(blocks.data(), blocks.size(), &stride)) {
+        a.blk_first = blocks[0];
+        a.blk_stride = stride;
+        a.nblk = blocks.size();
+        return launch();
+    }
+    return with_block_lists(dev, stream, blocks.data(), blocks.size(), [&](const uint32_t* d_list, uint64_t cnt) {
+        a.blk_list = d_list;
+        a.nblk = cnt;
+        return launch();
+    });
+}
 }  // namespace
 
 int refuse_capture(int dev, hipStream_t stream) {
@@ -1001,6 +1019,21 @@ int refuse_capture(int dev, hipStream_t stream) {
     if ((rc = capture_state(stream, &capturing))) return rc;
     return capturing ? SHMR_EC_INVALID_ARGUMENT : SHMR_EC_OK;
 }
+
+namespace {
+// What the calls over a degraded batch in one slab open with: a capture is
+// refused before anything is enqueued (shmr_ec.h); the blocks by presence
+// pattern, complete ones included (none: an empty batch, nothing to do); the
+// in-place layout.
+int degraded_batch(const Codec& c, int dev, hipStream_t stream, uint8_t* d_shards, uint64_t shard_pitch,
+                   uint64_t block_pitch, const uint8_t* present, uint64_t nblocks, PatternGroups* groups, Layout* L) {
+    const int rc = refuse_capture(dev, stream);
+    if (rc || nblocks == 0) return rc;
+    if (nblocks > 0xffffffffull) return SHMR_EC_INVALID_ARGUMENT;   // block lists are 32-bit
+    *L = Layout{d_shards, d_shards, block_pitch, shard_pitch, block_pitch, shard_pitch, 0};
+    return group_patterns(c, present, nblocks, nullptr, true, groups);
+}
+}  // namespace
 
 int launch_set(Plan& plan, int dev, const Layout& L, const BlockSet& bs, uint64_t len, hipStream_t stream,
                OpClass op) {
@@ -1219,24 +1252,59 @@ int locate_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
 }
 
 // ===========================================================================
-// Parity delta update.  The pieces come in round order; a table chunk holds
-// up to kUpdateTablePieces of them (one ring slot) and fewer than 2^31 tiles,
-// and the pieces of each round in it are one launch.  Two pieces of one round
-// in different chunks run in different launches, which is as good: rounds only
-// keep pieces with intersecting footprints out of one launch.
+// Ranged pieces (piece_plan.hpp), shared by the update and the read below: the
+// pieces `ps` as tables of `Entry`, a ring slot per chunk of
+// piece::chunk_pieces.  entry(piece, vec, tile0) gives a piece's table entry;
+// launch(table, c0, cnt, tiles) enqueues the launches of the chunk of cnt pieces
+// from piece c0 on its device copy.  vec: 16-byte accesses -- anywhere where
+// the device serves unaligned ones, else only where every address of the piece
+// is aligned (its columns are): base16 says so of the shards' side, `flat` is
+// the base of the buffer Piece::flat counts in.
+// ===========================================================================
+namespace {
+static_assert(piece::kSlotBytes == UploadRing::kSlotBytes, "one ring slot per chunk");
+
+template <class Entry, class EntryOf, class Launch>
+int with_piece_tables(int dev, hipStream_t stream, const std::vector<piece::Piece>& ps, const void* flat, bool base16,
+                      EntryOf entry, Launch launch) {
+    const bool uvec = unaligned_vector(dev);
+    for (size_t c0 = 0; c0 < ps.size();) {
+        const size_t cnt = piece::chunk_pieces<Entry>(ps, c0);
+        uint32_t tiles = 0;
+        const int rc = with_table(
+            dev, stream, cnt * sizeof(Entry),
+            [&](uint8_t* h) {
+                Entry* dp = reinterpret_cast<Entry*>(h);
+                for (size_t i = 0; i < cnt; ++i) {
+                    const piece::Piece& p = ps[c0 + i];
+                    const bool vec = p.vec && (uvec || (base16 && aligned16(uintptr_t(flat) + p.flat)));
+                    dp[i] = entry(p, vec ? piece::kVecFlag : 0u, tiles);
+                    tiles += piece::piece_tiles(p.len);
+                }
+            },
+            [&](const uint8_t* d) -> int { return launch(reinterpret_cast<const Entry*>(d), c0, cnt, tiles); });
+        if (rc) return rc;
+        c0 += cnt;
+    }
+    return SHMR_EC_OK;
+}
+}  // namespace
+
+// ===========================================================================
+// Parity delta update.  The pieces come in round order, and the pieces of each
+// round in a table chunk are one launch.  Two pieces of one round in different
+// chunks run in different launches, which is as good: rounds only keep pieces
+// with intersecting footprints out of one launch.
 // ===========================================================================
 int update_on_device(Codec& c, int dev, const Layout& L, const update::Plan& up, const uint8_t* d_src,
                      hipStream_t stream) {
-    static_assert(kUpdateTablePieces * sizeof(update::DevPiece) == UploadRing::kSlotBytes, "one ring slot per chunk");
+    static_assert(update::kTablePieces * sizeof(update::DevPiece) == UploadRing::kSlotBytes, "a slot is whole entries");
     int rc = refuse_capture(dev, stream);
     if (rc) return rc;
     Plan& plan = *c.encode_plan();
     const uint8_t* dplan = nullptr;
     rc = plan_on_device(plan, dev, stream, false, &dplan);
     if (rc) return rc;
-    // 16-byte accesses: anywhere where the device serves unaligned ones, else
-    // only where every address of the piece is aligned (its columns are)
-    const bool uvec = unaligned_vector(dev), base16 = layout_aligned16(L);
     kern::UpdateArgs u{};
     u.data = const_cast<uint8_t*>(L.in_base);
     u.parity = L.out_base;
@@ -1248,48 +1316,28 @@ int update_on_device(Codec& c, int dev, const Layout& L, const update::Plan& up,
     u.par_spitch = L.out_spitch;
     u.p = plan.m;
     const std::vector<update::Piece>& ps = up.pieces;
-    for (size_t c0 = 0; c0 < ps.size();) {
-        size_t cnt = 0;
-        uint64_t tiles = 0;
-        while (c0 + cnt < ps.size() && cnt < kUpdateTablePieces) {
-            const uint64_t t = update::piece_tiles(ps[c0 + cnt].len);
-            if (tiles + t > 0x7fffffffull) break;
-            tiles += t;
-            ++cnt;
-        }
-        rc = with_table(
-            dev, stream, cnt * sizeof(update::DevPiece),
-            [&](uint8_t* h) {
-                update::DevPiece* dp = reinterpret_cast<update::DevPiece*>(h);
-                uint32_t tile0 = 0;
-                for (size_t i = 0; i < cnt; ++i) {
-                    const update::Piece& p = ps[c0 + i];
-                    const bool vec = p.vec && (uvec || (base16 && aligned16(uintptr_t(d_src) + p.src)));
-                    dp[i] = update::DevPiece{p.col, p.src, p.block, p.len, p.shard | (vec ? update::kVecFlag : 0u), tile0};
-                    tile0 += update::piece_tiles(p.len);
-                }
-            },
-            [&](const uint8_t* d) -> int {
-                uint32_t tile0 = 0;
-                for (size_t i = 0; i < cnt;) {   // the chunk's pieces of one round
-                    size_t j = i;
-                    uint32_t nt = 0;
-                    for (; j < cnt && ps[c0 + j].round == ps[c0 + i].round; ++j) nt += update::piece_tiles(ps[c0 + j].len);
-                    u.pieces = reinterpret_cast<const update::DevPiece*>(d) + i;
-                    u.npieces = uint32_t(j - i);
-                    u.tile_base = tile0;
-                    u.ntiles = nt;
-                    count_device(dev, kDevLaunches);
-                    SHMR_HIP_TRY(kern::launch_update(u, stream));
-                    tile0 += nt;
-                    i = j;
-                }
-                return SHMR_EC_OK;
-            });
-        if (rc) return rc;
-        c0 += cnt;
-    }
-    return SHMR_EC_OK;
+    return with_piece_tables<update::DevPiece>(
+        dev, stream, ps, d_src, layout_aligned16(L),
+        [](const update::Piece& p, uint32_t vec, uint32_t tile0) {
+            return update::DevPiece{p.col, p.flat, p.block, p.len, p.shard | vec, tile0};
+        },
+        [&](const update::DevPiece* d, size_t c0, size_t cnt, uint32_t) -> int {
+            uint32_t tile0 = 0;
+            for (size_t i = 0; i < cnt;) {   // the chunk's pieces of one round
+                size_t j = i;
+                uint32_t nt = 0;
+                for (; j < cnt && ps[c0 + j].round == ps[c0 + i].round; ++j) nt += update::piece_tiles(ps[c0 + j].len);
+                u.pieces = d + i;
+                u.npieces = uint32_t(j - i);
+                u.tile_base = tile0;
+                u.ntiles = nt;
+                count_device(dev, kDevLaunches);
+                SHMR_HIP_TRY(kern::launch_update(u, stream));
+                tile0 += nt;
+                i = j;
+            }
+            return SHMR_EC_OK;
+        });
 }
 
 // ===========================================================================
@@ -1300,7 +1348,7 @@ int update_on_device(Codec& c, int dev, const Layout& L, const update::Plan& up,
 // ===========================================================================
 int read_on_device(Codec& c, int dev, const uint8_t* d_shards, uint64_t shard_pitch, uint64_t block_pitch,
                    const uint8_t* present, const std::vector<read::Piece>& ps, uint8_t* d_dst, hipStream_t stream) {
-    static_assert(read::kSlotBytes == UploadRing::kSlotBytes, "one ring slot per chunk");
+    static_assert(read::kTablePieces * sizeof(read::DevPiece) <= UploadRing::kSlotBytes, "one ring slot per chunk");
     int rc = refuse_capture(dev, stream);
     if (rc) return rc;
     const unsigned k = c.k(), t = k + c.p();
@@ -1328,9 +1376,6 @@ int read_on_device(Codec& c, int dev, const uint8_t* d_shards, uint64_t shard_pi
         }
         of_block[p.block] = &it->second;
     }
-    // 16-byte accesses: anywhere where the device serves unaligned ones, else
-    // only where every address of the piece is aligned (its columns are)
-    const bool uvec = unaligned_vector(dev);
     const bool base16 = aligned16(uintptr_t(d_shards)) && aligned16(shard_pitch) && aligned16(block_pitch);
     kern::ReadArgs a{};
     a.shards = d_shards;
@@ -1338,40 +1383,24 @@ int read_on_device(Codec& c, int dev, const uint8_t* d_shards, uint64_t shard_pi
     a.bpitch = block_pitch;
     a.spitch = shard_pitch;
     a.k = k;
-    for (size_t c0 = 0; c0 < ps.size();) {
-        const size_t cnt = read::chunk_pieces(ps, c0);
-        uint32_t tiles = 0;
-        rc = with_table(
-            dev, stream, cnt * sizeof(read::DevPiece),
-            [&](uint8_t* h) {
-                read::DevPiece* dp = reinterpret_cast<read::DevPiece*>(h);
-                for (size_t i = 0; i < cnt; ++i) {
-                    const read::Piece& p = ps[c0 + i];
-                    const bool vec = p.vec && (uvec || (base16 && aligned16(uintptr_t(d_dst) + p.dst)));
-                    uint32_t sf = p.shard, flags = vec ? read::kVecFlag : 0u;
-                    uint64_t plan = 0;
-                    if (!present[uint64_t(p.block) * t + p.shard]) {
-                        const Pattern& pat = *of_block.find(p.block)->second;
-                        sf = pat.row_of[p.shard];
-                        plan = uint64_t(uintptr_t(pat.dplan));
-                        flags |= read::kRebuildFlag;
-                    }
-                    dp[i] = read::DevPiece{p.col, p.dst, plan, p.block, p.len, sf | flags, tiles};
-                    tiles += read::piece_tiles(p.len);
-                }
-            },
-            [&](const uint8_t* d) -> int {
-                a.pieces = reinterpret_cast<const read::DevPiece*>(d);
-                a.npieces = uint32_t(cnt);
-                a.ntiles = tiles;
-                count_device(dev, kDevLaunches);
-                SHMR_HIP_TRY(kern::launch_read(a, stream));
-                return SHMR_EC_OK;
-            });
-        if (rc) return rc;
-        c0 += cnt;
-    }
-    return SHMR_EC_OK;
+    return with_piece_tables<read::DevPiece>(
+        dev, stream, ps, d_dst, base16,
+        [&](const read::Piece& p, uint32_t vec, uint32_t tile0) {
+            if (present[uint64_t(p.block) * t + p.shard])
+                return read::DevPiece{p.col, p.flat, 0, p.block, p.len, p.shard | vec, tile0};
+            const Pattern& pat = *of_block.find(p.block)->second;
+            return read::DevPiece{p.col,   p.flat, uint64_t(uintptr_t(pat.dplan)),
+                                  p.block, p.len,  pat.row_of[p.shard] | vec | read::kRebuildFlag,
+                                  tile0};
+        },
+        [&](const read::DevPiece* d, size_t, size_t cnt, uint32_t tiles) -> int {
+            a.pieces = d;
+            a.npieces = uint32_t(cnt);
+            a.ntiles = tiles;
+            count_device(dev, kDevLaunches);
+            SHMR_HIP_TRY(kern::launch_read(a, stream));
+            return SHMR_EC_OK;
+        });
 }
 
 int validate_presence(const Codec& c, const uint8_t* present, uint64_t nblocks) {
@@ -1517,18 +1546,14 @@ int checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch
                       const uint8_t* present, uint64_t nblocks, uint64_t len, bool data_only, bool no_rebuild,
                       uint32_t* d_mismatch, hipStream_t stream) {
     const unsigned k = c.k(), t = k + c.p();
-    // Not inside a graph capture (shmr_ec.h): refused before anything is enqueued.
-    int rc = refuse_capture(dev, stream);
-    if (rc) return rc;
-    if (nblocks == 0) return SHMR_EC_OK;
-    if (nblocks > 0xffffffffull) return SHMR_EC_INVALID_ARGUMENT;   // block lists are 32-bit
     PatternGroups groups;
-    if ((rc = group_patterns(c, present, nblocks, nullptr, true, &groups))) return rc;
+    Layout L{};
+    int rc = degraded_batch(c, dev, stream, d_shards, shard_pitch, block_pitch, present, nblocks, &groups, &L);
+    if (rc || groups.empty()) return rc;
     const auto complete = groups.find(std::vector<uint8_t>(t, 1));
     SHMR_HIP_TRY(hipMemsetAsync(d_mismatch, 0, size_t(nblocks) * sizeof(uint32_t), stream));
     count_device(dev, kDevBlocksVerified, nblocks);
     count_device(dev, kDevBlocksReconstructed, nblocks - (complete == groups.end() ? 0 : complete->second.size()));
-    const Layout L{d_shards, d_shards, block_pitch, shard_pitch, block_pitch, shard_pitch, 0};
     for (auto& g : groups) {
         const std::shared_ptr<Plan> planp = c.checked_plan(g.first, data_only, no_rebuild);
         Plan& plan = *planp;
@@ -1545,21 +1570,8 @@ int checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch
             for (uint32_t r = nstore; r < rows; ++r) bits[r] = std::min<uint32_t>(plan.out_idx[row0 + r] - k, 31);
             return kern::launch_check(a, d_mismatch, rows, nstore, bits, mode, stream);
         };
-        auto launch_groups = [&]() { return compare_groups(dev, L, a, plan.m, len, tile_4k, launch); };
-        const std::vector<uint64_t>& blocks = g.second;
-        uint64_t stride = 1;
-        if (arith_stride(blocks.data(), blocks.size(), &stride)) {
-            a.blk_first = blocks[0];
-            a.blk_stride = stride;
-            a.nblk = blocks.size();
-            rc = launch_groups();
-        } else {
-            rc = with_block_lists(dev, stream, blocks.data(), blocks.size(), [&](const uint32_t* d_list, uint64_t cnt) {
-                a.blk_list = d_list;
-                a.nblk = cnt;
-                return launch_groups();
-            });
-        }
+        rc = over_blocks(dev, stream, a, g.second,
+                         [&]() { return compare_groups(dev, L, a, plan.m, len, tile_4k, launch); });
         if (rc) return rc;
     }
     return SHMR_EC_OK;
@@ -1578,13 +1590,10 @@ int locate_checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shar
                              const uint8_t* present, uint64_t nblocks, uint64_t len, bool data_only, bool no_rebuild,
                              uint32_t* d_mismatch, int32_t* d_located, uint32_t* d_cand, hipStream_t stream) {
     const unsigned k = c.k();
-    // Not inside a graph capture (shmr_ec.h): refused before anything is enqueued.
-    int rc = refuse_capture(dev, stream);
-    if (rc) return rc;
-    if (nblocks == 0) return SHMR_EC_OK;
-    if (nblocks > 0xffffffffull) return SHMR_EC_INVALID_ARGUMENT;   // block lists are 32-bit
     PatternGroups groups;
-    if ((rc = group_patterns(c, present, nblocks, nullptr, true, &groups))) return rc;
+    Layout L{};
+    int rc = degraded_batch(c, dev, stream, d_shards, shard_pitch, block_pitch, present, nblocks, &groups, &L);
+    if (rc || groups.empty()) return rc;
     // every pattern's plans, before anything is enqueued
     struct Located {
         std::shared_ptr<Plan> compare, ratio;   // null below two surplus shards
@@ -1608,7 +1617,6 @@ int locate_checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shar
                            d_mismatch, stream);
     if (rc) return rc;
     SHMR_HIP_TRY(kern::launch_locate_preset(d_cand, nblocks, k, stream));
-    const Layout L{d_shards, d_shards, block_pitch, shard_pitch, block_pitch, shard_pitch, 0};
     size_t gi = 0;
     for (auto& g : groups) {
         const Located& lp = plans[gi++];
@@ -1621,7 +1629,7 @@ int locate_checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shar
             a = apply_args(L, *lp.compare, dplan, len);
         }
         // the pattern's locate (s >= 2) and resolve launches over the blocks `a` names
-        auto launch_pattern = [&]() -> int {
+        rc = over_blocks(dev, stream, a, g.second, [&]() -> int {
             if (lp.s >= 2) {
                 const uint8_t* qtab = dratio + plan_tab_off(lp.ratio->k, lp.ratio->m);
                 const int lrc = compare_groups(dev, L, a, locate::rows_used(lp.s), len, tile_4k,
@@ -1635,21 +1643,7 @@ int locate_checked_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shar
                 a, d_mismatch, d_cand, d_located, dplan ? reinterpret_cast<const uint16_t*>(dplan + 8) : nullptr, lp.s,
                 lp.mask, stream));
             return SHMR_EC_OK;
-        };
-        const std::vector<uint64_t>& blocks = g.second;
-        uint64_t stride = 1;
-        if (arith_stride(blocks.data(), blocks.size(), &stride)) {
-            a.blk_first = blocks[0];
-            a.blk_stride = stride;
-            a.nblk = blocks.size();
-            rc = launch_pattern();
-        } else {
-            rc = with_block_lists(dev, stream, blocks.data(), blocks.size(), [&](const uint32_t* d_list, uint64_t cnt) {
-                a.blk_list = d_list;
-                a.nblk = cnt;
-                return launch_pattern();
-            });
-        }
+        });
         if (rc) return rc;
     }
     return SHMR_EC_OK;

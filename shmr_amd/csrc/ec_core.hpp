@@ -294,11 +294,10 @@ int locate_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
 // (update_plan.hpp, validated by the caller) applied to blocks laid out per
 // `L` as for encode_on_device (L.in_base: the data, written here too), the new
 // bytes read from d_src.  The piece table travels through the upload ring in
-// chunks of kUpdateTablePieces; behind each chunk one launch per round present
-// in it, rounds in ascending order on `stream`.  Stream-ordered, no blocking
-// call after device init; a stream that is being captured is refused
+// the chunks of piece::chunk_pieces; behind each chunk one launch per round
+// present in it, rounds in ascending order on `stream`.  Stream-ordered, no
+// blocking call after device init; a stream that is being captured is refused
 // (INVALID_ARGUMENT, nothing enqueued).
-constexpr size_t kUpdateTablePieces = 256 * 1024 / 32;   // UploadRing::kSlotBytes / sizeof(update::DevPiece)
 int update_on_device(Codec& c, int dev, const Layout& L, const update::Plan& up, const uint8_t* d_src,
                      hipStream_t stream);
 // Ranged reads (shmr_ec_read_batch_dev): the planned pieces `ps`
@@ -307,7 +306,7 @@ int update_on_device(Codec& c, int dev, const Layout& L, const update::Plan& up,
 // shard is a copy; a piece of an absent one names the device image of its
 // pattern's data-only reconstruct plan (the per-pattern cache, uploaded on
 // `stream` on first use) and its row there.  The piece table travels through
-// the upload ring in the chunks of read::chunk_pieces, one launch behind each;
+// the upload ring in the chunks of piece::chunk_pieces, one launch behind each;
 // blocks of different patterns share a launch.  Stream-ordered, no blocking
 // call after device init; a stream that is being captured is refused
 // (INVALID_ARGUMENT, nothing enqueued).  Nothing but d_dst is written.

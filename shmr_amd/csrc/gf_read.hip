@@ -15,7 +15,7 @@
 //
 //  * Work mapping: one workgroup per 4 KiB tile of a piece, found by the
 //    binary search over the pieces' tile prefixes that the update kernel runs
-//    (update::find_piece, DevPiece::tile0): log2(pieces) scalar loads of one
+//    (gf_piece.hpp lane_chunk, DevPiece::tile0): log2(pieces) scalar loads of one
 //    workgroup-uniform word.  Blocks of different presence patterns share a
 //    launch: a rebuild piece carries the address of its own plan image and its
 //    row in it.
@@ -45,27 +45,13 @@
 // Not a gf_apply_kernel instantiation and not part of shmr_ec_kernel_inventory.
 #include <hip/hip_runtime.h>
 
-#include "gf_tile.hpp"
+#include "gf_piece.hpp"
 #include "read_plan.hpp"
 
 namespace shmr {
 namespace kern {
 
 namespace {
-
-static_assert(read::kTileBytes == uint32_t(kThreads) * 16, "a tile is one 16-byte chunk per lane");
-
-template <bool VEC>
-__device__ __forceinline__ u32x4 read_load(const uint8_t* q, int64_t n) {
-    if constexpr (VEC) return load16<0>(q);
-    else return load_bytes(q, n);
-}
-
-template <bool VEC>
-__device__ __forceinline__ void read_store(uint8_t* q, const u32x4& v, int64_t n) {
-    if constexpr (VEC) store16<0>(q, v);
-    else store_bytes(q, v, n);
-}
 
 // The lane's n bytes (VEC: n = 16) of row `row` of the plan image: b is the
 // lane's column of shard 0 of the block, out where the bytes go.
@@ -81,35 +67,25 @@ __device__ __forceinline__ void rebuild_chunk(const uint8_t* b, uint64_t spitch,
         mac<1, 0>(acc, v, tb);
     };
     uint32_t acc[1][4] = {{0u, 0u, 0u, 0u}};
-    u32x4 cur = read_load<VEC>(b + uint64_t(plan_u16(in_idx, 0)) * spitch, n);
+    u32x4 cur = piece_load<VEC>(b + uint64_t(plan_u16(in_idx, 0)) * spitch, n);
     uint32_t t = 0;
     for (; t + 1 < k; ++t) {
-        const u32x4 nxt = read_load<VEC>(b + uint64_t(plan_u16(in_idx, t + 1)) * spitch, n);
+        const u32x4 nxt = piece_load<VEC>(b + uint64_t(plan_u16(in_idx, t + 1)) * spitch, n);
         __builtin_amdgcn_sched_barrier(0);
         step(acc, cur, t);
         __builtin_amdgcn_sched_barrier(0);
         cur = nxt;
     }
     step(acc, cur, t);
-    read_store<VEC>(out, u32x4{acc[0][0], acc[0][1], acc[0][2], acc[0][3]}, n);
+    piece_store<VEC>(out, u32x4{acc[0][0], acc[0][1], acc[0][2], acc[0][3]}, n);
 }
 
 __global__ __launch_bounds__(kThreads) void gf_read_kernel(const ReadArgs r) {
-    // The piece: workgroup-uniform, every word through scalar loads.
-    const cu32* pw = as_const<cu32>(r.pieces);
-    const uint32_t tile = blockIdx.x;
-    const uint32_t pi =
-        read::find_piece([&](uint32_t i) { return pw[size_t(i) * read::kPieceWords + 9]; }, r.npieces, tile);
-    const cu32* e = pw + size_t(pi) * read::kPieceWords;
-    const uint64_t col = uint64_t(e[0]) | (uint64_t(e[1]) << 32);
-    const uint64_t dst = uint64_t(e[2]) | (uint64_t(e[3]) << 32);
-    const uint64_t plan = uint64_t(e[4]) | (uint64_t(e[5]) << 32);
-    const uint32_t blk = e[6], len = e[7], sf = e[8], tile0 = e[9];
+    const LaneChunk c = lane_chunk<read::kPieceWords>(r.pieces, r.npieces, blockIdx.x);
+    const uint64_t col = piece_u64(c.e, 0), dst = piece_u64(c.e, 2), plan = piece_u64(c.e, 4);
+    const uint32_t blk = c.e[6], sf = c.e[8], pos = c.pos, n = c.n;
+    if (n == 0) return;   // (no barrier and no LDS in this kernel)
     const uint32_t shard = sf & ~(read::kVecFlag | read::kRebuildFlag);
-    // The lane's chunk: bytes [pos, pos + n) of the piece.
-    const uint32_t pos = (tile - tile0) * read::kTileBytes + threadIdx.x * 16u;
-    if (pos >= len) return;   // (no barrier and no LDS in this kernel)
-    const uint32_t n = len - pos < 16u ? len - pos : 16u;
     const uint8_t* b = r.shards + uint64_t(blk) * r.bpitch + col + pos;
     uint8_t* out = r.dst + dst + pos;
     const bool vec = (sf & read::kVecFlag) != 0;
@@ -119,8 +95,8 @@ __global__ __launch_bounds__(kThreads) void gf_read_kernel(const ReadArgs r) {
         else rebuild_chunk<false>(b, r.spitch, image, shard, r.k, out, int64_t(n));
     } else {
         const uint8_t* s = b + uint64_t(shard) * r.spitch;
-        if (vec) read_store<true>(out, read_load<true>(s, 16), 16);
-        else read_store<false>(out, read_load<false>(s, int64_t(n)), int64_t(n));
+        if (vec) piece_store<true>(out, piece_load<true>(s, 16), 16);
+        else piece_store<false>(out, piece_load<false>(s, int64_t(n)), int64_t(n));
     }
 }
 

@@ -10,7 +10,8 @@
 // pieces, the byte-exact footprint rule and the rounds).
 //
 //  * Work mapping: one workgroup per 4 KiB tile of a piece, found by a binary
-//    search over the pieces' tile prefixes (DevPiece::tile0), as seg_block does
+//    search over the pieces' tile prefixes (DevPiece::tile0; gf_piece.hpp
+//    lane_chunk, shared with the read kernel), as seg_block does
 //    over segments.  A per-tile descriptor would make the table as long as the
 //    written bytes / 4 KiB (a whole-shard write into each of 512 blocks: 65,536
 //    entries, 2 MiB, eight slots of the upload ring) where the prefix table is
@@ -38,7 +39,7 @@
 // Not a gf_apply_kernel instantiation and not part of shmr_ec_kernel_inventory.
 #include <hip/hip_runtime.h>
 
-#include "gf_tile.hpp"
+#include "gf_piece.hpp"
 #include "update_plan.hpp"
 
 namespace shmr {
@@ -46,27 +47,19 @@ namespace kern {
 
 namespace {
 
-static_assert(update::kTileBytes == uint32_t(kThreads) * 16, "a tile is one 16-byte chunk per lane");
-
 // The lane's n bytes (VEC: n = 16) at d (data), s (new bytes) and par (parity
 // row 0; row r at par + r * spitch).
 template <bool VEC>
 __device__ __forceinline__ void update_chunk(uint8_t* d, const uint8_t* s, uint8_t* par, uint64_t spitch,
                                              const uint8_t* tabs, uint32_t tab0, uint32_t p, int64_t n) {
-    auto load = [&](const uint8_t* q) {
-        if constexpr (VEC) return load16<0>(q);
-        else return load_bytes(q, n);
-    };
-    auto store = [&](uint8_t* q, const u32x4& v) {
-        if constexpr (VEC) store16<0>(q, v);
-        else store_bytes(q, v, n);
-    };
     auto row = [&](u32x4& acc, const u32x4& delta, uint32_t r) {
         const Tab tb[1] = {read_tab(tabs, tab0 + r)};
         uint32_t a[1][4] = {{acc.x, acc.y, acc.z, acc.w}};
         mac<1, 0>(a, delta, tb);
         acc = u32x4{a[0][0], a[0][1], a[0][2], a[0][3]};
     };
+    auto load = [&](const uint8_t* q) { return piece_load<VEC>(q, n); };
+    auto store = [&](uint8_t* q, const u32x4& v) { piece_store<VEC>(q, v, n); };
     const u32x4 oldv = load(d);
     const u32x4 newv = load(s);
     u32x4 cur = load(par);
@@ -88,19 +81,11 @@ __device__ __forceinline__ void update_chunk(uint8_t* d, const uint8_t* s, uint8
 }
 
 __global__ __launch_bounds__(kThreads) void gf_update_kernel(const UpdateArgs u) {
-    // The piece: workgroup-uniform, every word through scalar loads.
-    const cu32* pw = as_const<cu32>(u.pieces);
-    const uint32_t tile = u.tile_base + blockIdx.x;
-    const uint32_t pi = update::find_piece([&](uint32_t i) { return pw[size_t(i) * 8 + 7]; }, u.npieces, tile);
-    const cu32* e = pw + size_t(pi) * 8;
-    const uint64_t col = uint64_t(e[0]) | (uint64_t(e[1]) << 32);
-    const uint64_t src = uint64_t(e[2]) | (uint64_t(e[3]) << 32);
-    const uint32_t blk = e[4], len = e[5], sf = e[6], tile0 = e[7];
+    const LaneChunk c = lane_chunk<update::kPieceWords>(u.pieces, u.npieces, u.tile_base + blockIdx.x);
+    const uint64_t col = piece_u64(c.e, 0), src = piece_u64(c.e, 2);
+    const uint32_t blk = c.e[4], sf = c.e[6], pos = c.pos, n = c.n;
+    if (n == 0) return;   // (no barrier and no LDS in this kernel)
     const uint32_t shard = sf & ~update::kVecFlag;
-    // The lane's chunk: bytes [pos, pos + n) of the piece.
-    const uint32_t pos = (tile - tile0) * update::kTileBytes + threadIdx.x * 16u;
-    if (pos >= len) return;   // (no barrier and no LDS in this kernel)
-    const uint32_t n = len - pos < 16u ? len - pos : 16u;
     uint8_t* d = u.data + uint64_t(blk) * u.data_bpitch + uint64_t(shard) * u.data_spitch + col + pos;
     uint8_t* par = u.parity + uint64_t(blk) * u.par_bpitch + col + pos;
     const uint8_t* s = u.src + src + pos;

@@ -15,11 +15,8 @@
 //    16-byte stores inside [a, b), edge chunks are stored byte by byte.  Two
 //    pieces of one block may share a round iff their column ranges are
 //    disjoint, whatever their shards.
-//  * Pieces: an update [offset, offset + len) becomes a byte-granular head up
-//    to the next multiple of 16 (if offset is off one), vector pieces of whole
-//    16-column chunks (at most kMaxPieceBytes each), and a byte-granular tail.
-//    Chunks sit on multiples of 16 in COLUMN space: with 16-byte aligned
-//    bases and pitches they are aligned accesses of the shards.
+//  * Pieces: piece_plan.hpp (head, 16-byte vector run, tail; Piece::flat is the
+//    first byte in d_src), as are the range check and the table chunks.
 //  * Rounds: per block, interval colouring of the updates' column ranges in
 //    order of their first column -- an update takes the round of the range
 //    that ended first if it ended at or before its own first column, else a new
@@ -34,35 +31,19 @@
 #include <cstddef>
 #include <cstdint>
 #include <functional>
-#include <numeric>
 #include <queue>
 #include <utility>
 #include <vector>
 
+#include "piece_plan.hpp"
 #include "shmr_ec.h"
-
-#if defined(__HIP__)
-#define SHMR_UPDATE_HD __attribute__((host)) __attribute__((device))
-#else
-#define SHMR_UPDATE_HD
-#endif
 
 namespace shmr {
 namespace update {
 
-constexpr uint32_t kChunk = 16;                  // bytes of one vector access
-constexpr uint32_t kTileBytes = 256 * kChunk;    // columns one workgroup covers (kern::kThreads lanes)
-constexpr uint64_t kMaxPieceBytes = 1u << 30;    // a piece's length and tile count fit 32 bits
-constexpr bool kByteExactEdges = true;           // the footprint rule above (the checker prints it)
-constexpr uint32_t kVecFlag = 1u << 31;          // DevPiece::shard: whole 16-byte chunks, vector accesses
+using namespace piece;   // the range check, the split, the chunks and the tile search, shared with read_plan.hpp
 
-// One piece as the planner gives it, in round order.
-struct Piece {
-    uint64_t col, src;   // first column in the shard; first byte in d_src
-    uint64_t update;     // index of the update it is a part of
-    uint32_t block, shard, len, round;
-    bool vec;            // col and len are multiples of kChunk
-};
+constexpr bool kByteExactEdges = true;           // the footprint rule above (the checker prints it)
 
 // One piece as the kernel reads it (32 bytes, scalar dword loads).
 struct DevPiece {
@@ -72,21 +53,9 @@ struct DevPiece {
     uint32_t tile0;   // tiles of the table's pieces in front of this one
 };
 static_assert(sizeof(DevPiece) == 32, "the kernel indexes the table in 8-dword entries");
-
-SHMR_UPDATE_HD inline uint32_t piece_tiles(uint32_t len) { return (len + kTileBytes - 1) / kTileBytes; }
-
-// The piece of pieces [0, n) that holds `tile`: the last one whose tile0 is
-// <= tile (tile0(i) ascending, tile0(0) <= tile, every piece has >= 1 tile).
-template <class Tile0>
-SHMR_UPDATE_HD inline uint32_t find_piece(Tile0 tile0, uint32_t n, uint32_t tile) {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (tile0(mid) <= tile) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
+constexpr uint32_t kPieceWords = sizeof(DevPiece) / 4;
+// (8192 pieces of kMaxPieceBytes are exactly 2^31 tiles: the tile bound of chunk_pieces is live here)
+constexpr size_t kTablePieces = kSlotBytes / sizeof(DevPiece);
 
 struct Plan {
     std::vector<uint32_t> round_of;   // per update
@@ -94,43 +63,16 @@ struct Plan {
     std::vector<Piece> pieces;        // ascending round
 };
 
-inline bool valid(const shmr_ec_update& u, uint64_t nblocks, unsigned k, uint64_t shard_len, uint64_t src_bytes) {
-    // (no sum is formed: offset + len and src_offset + len may pass 2^64)
-    return u.block < nblocks && u.shard < k && u.len != 0 && u.len <= shard_len && u.offset <= shard_len - u.len &&
-           u.len <= src_bytes && u.src_offset <= src_bytes - u.len;
-}
-
-inline void split(const shmr_ec_update& u, uint64_t index, uint32_t round, std::vector<Piece>* out) {
-    uint64_t col = u.offset, src = u.src_offset, left = u.len;
-    auto emit = [&](uint64_t n, bool vec) {
-        out->push_back(Piece{col, src, index, u.block, u.shard, uint32_t(n), round, vec});
-        col += n;
-        src += n;
-        left -= n;
-    };
-    if (col % kChunk) emit(std::min<uint64_t>(left, kChunk - col % kChunk), false);
-    while (left >= kChunk) emit(std::min<uint64_t>(left / kChunk * kChunk, kMaxPieceBytes), true);
-    if (left) emit(left, false);
-}
-
 // False: an update is out of range, or two of one (block, shard) intersect
 // (*out is unspecified then).  pieces = false: rounds only.
 inline bool plan(const shmr_ec_update* u, size_t n, uint64_t nblocks, unsigned k, uint64_t shard_len,
                  uint64_t src_bytes, Plan* out, bool pieces = true) {
     for (size_t i = 0; i < n; ++i)
-        if (!valid(u[i], nblocks, k, shard_len, src_bytes)) return false;
-    std::vector<size_t> order(n);
-    std::iota(order.begin(), order.end(), size_t(0));
+        if (!valid(u[i], u[i].src_offset, nblocks, k, shard_len, src_bytes)) return false;
     // two writes to one byte of a shard: their order would be undefined
-    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-        if (u[a].block != u[b].block) return u[a].block < u[b].block;
-        if (u[a].shard != u[b].shard) return u[a].shard < u[b].shard;
-        return u[a].offset < u[b].offset;
-    });
-    for (size_t i = 1; i < n; ++i) {
-        const shmr_ec_update &a = u[order[i - 1]], &b = u[order[i]];
-        if (a.block == b.block && a.shard == b.shard && a.offset + a.len > b.offset) return false;
-    }
+    std::vector<size_t> order;
+    auto key = [&](size_t i) { return Key{uint64_t(u[i].block) << 32 | u[i].shard, u[i].offset, u[i].len}; };
+    if (!disjoint(n, key, &order)) return false;
     // rounds: per block, the ranges in order of their first column
     std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
         if (u[a].block != u[b].block) return u[a].block < u[b].block;
@@ -162,7 +104,7 @@ inline bool plan(const shmr_ec_update* u, size_t n, uint64_t nblocks, unsigned k
     if (!pieces) return true;
     std::vector<Piece> all;
     all.reserve(n);
-    for (size_t i = 0; i < n; ++i) split(u[i], i, out->round_of[i], &all);
+    for (size_t i = 0; i < n; ++i) split(u[i], u[i].src_offset, i, out->round_of[i], &all);
     // ascending round, stable (a counting sort)
     std::vector<size_t> at(size_t(out->nrounds) + 1, 0);
     for (const Piece& p : all) ++at[p.round + 1];

@@ -311,14 +311,17 @@ class ReedSolomon:
         tuple (clean, repaired, not repairable).  Waits on torch's current
         stream; not capturable."""
         B, dsp, dbp, psp, pbp, L = self._device_regions(data, parity, shard_len, "scrub_batch_dev")
+        return self._located_counts(self._L.shmr_ec_scrub_batch_dev, data, device, B, ctypes.c_void_p(data.data_ptr()),
+                                    dsp, dbp, ctypes.c_void_p(parity.data_ptr()), psp, pbp, B, L)
+
+    def _located_counts(self, fn, like, device, B: int, *head):
+        """A blocking locate-and-repair call ``fn(handle, *head, located, counts, device, stream)`` on the
+        current stream of ``like`` -> ``(located int32 [B], (clean, repaired, not repairable))``."""
         located = np.zeros(B, dtype=np.int32)
         counts = (ctypes.c_uint64 * 3)()
-        dev, stream = self._stream_and_device(data)
-        dev = dev if device is None else int(device)
-        _check(self._L.shmr_ec_scrub_batch_dev(self._h, ctypes.c_void_p(data.data_ptr()), dsp, dbp,
-                                               ctypes.c_void_p(parity.data_ptr()), psp, pbp, B, L,
-                                               located.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), counts,
-                                               dev, stream))
+        dev, stream = self._stream_and_device(like)
+        _check(fn(self._h, *head, located.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), counts,
+                  dev if device is None else int(device), stream))
         return located, tuple(int(x) for x in counts)
 
     def scrub_shards_dev(self, shards, shard_len: Optional[int] = None, device: Optional[int] = None):
@@ -336,6 +339,17 @@ class ReedSolomon:
         ``(block, shard, offset, length, src_offset)`` or an ``(n, 5)`` integer
         array.  Values the C fields cannot hold are an ``InvalidArgument``."""
         return cls._request_array(updates, cls._UPDATE_DTYPE, "updates", "an update", "src_offset")
+
+    @staticmethod
+    def _flat_u8_on(tensor, name: str, like) -> None:
+        """The flat buffer of ``update_batch_dev`` (``src``) and ``read_batch_dev``
+        (``dst``): a 1-D contiguous uint8 tensor on the GPU of ``like``."""
+        import torch
+        if (not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.uint8 or tensor.dim() != 1
+                or (tensor.numel() > 1 and tensor.stride(0) != 1)):
+            raise TypeError(f"{name} must be a 1-D contiguous torch.uint8 tensor")
+        if tensor.device != like.device:
+            raise TypeError(f"{name} must be on {like.device}")
 
     @staticmethod
     def _request_array(rows, dtype, plural: str, one: str, last: str) -> np.ndarray:
@@ -394,13 +408,8 @@ class ReedSolomon:
         else is written.  Two updates must not intersect in one (block, shard).
         Enqueued on torch's current stream; not for graph capture (the native
         call refuses a stream that is being captured)."""
-        import torch
         B, dsp, dbp, psp, pbp, L = self._device_regions(data, parity, shard_len, "update_batch_dev")
-        if (not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.dim() != 1
-                or (src.numel() > 1 and src.stride(0) != 1)):
-            raise TypeError("src must be a 1-D contiguous torch.uint8 tensor")
-        if src.device != data.device:
-            raise TypeError(f"src must be on {data.device}")
+        self._flat_u8_on(src, "src", data)
         ua = self._update_array(updates)
         dev, stream = self._stream_and_device(data)
         dev = dev if device is None else int(device)
@@ -478,7 +487,6 @@ class ReedSolomon:
         checked for damage (``reconstruct_checked_batch_dev`` does that).
         Enqueued on torch's current stream; not for graph capture (the native
         call refuses a stream that is being captured)."""
-        import torch
         if shards.dim() != 3:
             raise TypeError("shards must be a [blocks, total, bytes] tensor")
         B, t = shards.shape[0], self.total_shard_count()
@@ -489,11 +497,7 @@ class ReedSolomon:
             raise ValueError(f"present must hold {B} x {t} flags")
         pr = pr.reshape(B, t)
         self._check_addressable(shards)
-        if (not isinstance(dst, torch.Tensor) or dst.dtype != torch.uint8 or dst.dim() != 1
-                or (dst.numel() > 1 and dst.stride(0) != 1)):
-            raise TypeError("dst must be a 1-D contiguous torch.uint8 tensor")
-        if dst.device != shards.device:
-            raise TypeError(f"dst must be on {shards.device}")
+        self._flat_u8_on(dst, "dst", shards)
         ra = self._read_array(reads)
         dev, stream = self._stream_and_device(shards)
         dev = dev if device is None else int(device)
@@ -712,14 +716,10 @@ class ReedSolomon:
         differs demoted to -2, and the dict ``{"clean", "repaired",
         "not_repairable"}``.  Waits on torch's current stream; not capturable."""
         B, L, pr = self._degraded_batch(shards, present, shard_len, "reconstruct_repair_batch_dev")
-        located = np.zeros(B, dtype=np.int32)
-        counts = (ctypes.c_uint64 * 3)()
-        dev, stream = self._stream_and_device(shards)
-        dev = dev if device is None else int(device)
-        _check(self._L.shmr_ec_reconstruct_repair_batch_dev(
-            self._h, ctypes.c_void_p(shards.data_ptr()), shards.stride(1), shards.stride(0), _ptr(pr), B, L,
-            located.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), counts, dev, stream))
-        return located, dict(zip(("clean", "repaired", "not_repairable"), (int(x) for x in counts)))
+        located, counts = self._located_counts(
+            self._L.shmr_ec_reconstruct_repair_batch_dev, shards, device, B, ctypes.c_void_p(shards.data_ptr()),
+            shards.stride(1), shards.stride(0), _ptr(pr), B, L)
+        return located, dict(zip(("clean", "repaired", "not_repairable"), counts))
 
     def locate_checked_plan(self, present: Sequence[bool]):
         """(in_idx, out_idx, ratio_rows, row_mask) of what the degraded locate

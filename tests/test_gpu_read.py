@@ -232,6 +232,31 @@ def test_whole_shard_equals_reconstruct_out(gpu):
     assert np.array_equal(got.reshape(c.B, S), out.cpu().numpy()[:, 0, :S])
 
 
+def test_read_after_update_of_the_same_range(gpu):
+    """A range written by update_shards_dev and read back, lost shard and present:
+    bytes [4090, 4113) of a shard are a 6-byte head, one vector piece at column
+    4096 and a 1-byte tail in both kernels, whose pieces share one table lookup."""
+    import torch
+    k, p, b, s, off, n, src_off, dst_off = 4, 2, 1, 1, 4090, 23, 7, 33
+    c = Case(k, p, [[1] * (k + p)] * 3, gpu)                         # pitch 4128 over shard_len 4117
+    new = np.random.default_rng(5).integers(0, 256, 64, dtype=np.uint8)
+    want = np.array(c.full)
+    want[b, s, off:off + n] = new[src_off:src_off + n]
+    rs_oracle.ReedSolomon(k, p).encode([want[b, i] for i in range(k + p)])
+    c.rs.update_shards_dev(c.shards, [(b, s, off, n, src_off)], torch.from_numpy(new).to(gpu), shard_len=S)
+    assert c.rs.verify_shards_dev(c.shards, shard_len=S).cpu().tolist() == [0, 0, 0]
+    img = c.img.copy()
+    img[c.off:c.off + c.B * (k + p) * c.pitch].reshape(c.B, k + p, c.pitch)[:, :, :S] = want
+    assert np.array_equal(c.buf.cpu().numpy(), img), "the update wrote other bytes than the oracle's"
+    for present in ([0 if (i, j) == (b, s) else 1 for i in range(c.B) for j in range(k + p)], [1] * (c.B * (k + p))):
+        dst = torch.full((96,), CANARY, dtype=torch.uint8, device=gpu)
+        c.rs.read_batch_dev(c.shards, np.array(present, np.uint8), [(b, s, off, n, dst_off)], dst, shard_len=S)
+        expect = np.full(96, CANARY, np.uint8)
+        expect[dst_off:dst_off + n] = want[b, s, off:off + n]
+        assert np.array_equal(dst.cpu().numpy(), expect), f"present={present[b * (k + p) + s]}"
+    assert np.array_equal(c.buf.cpu().numpy(), img), "a read wrote the shards"
+
+
 def test_capturing_stream_is_refused(gpu):
     """On a stream that is being captured the call returns InvalidArgument and
     enqueues nothing; the destination is untouched."""

@@ -13,7 +13,7 @@ a shard pitch above len (rounded up to 64) whose padding holds random bytes
 that are not a codeword.  `shift` moves both regions off 16-byte alignment.
 
 The piece table travels in chunks of 8,192 pieces (one 256 KiB slot of the
-upload ring, 32 bytes a piece: ec_core.hpp kUpdateTablePieces); the many-pieces
+upload ring, 32 bytes a piece: update_plan.hpp kTablePieces); the many-pieces
 test uses 8,192 + 1,025 one-byte updates, more than one chunk.
 """
 import numpy as np

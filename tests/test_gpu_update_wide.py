@@ -25,14 +25,14 @@ from test_gpu_update import Case, _case, shapes
 pytestmark = pytest.mark.gpu
 
 # ---- the product constants under test, mirrored once ----------------------------
-TABLE_CHUNK = 256 * 1024 // 32   # ec_core.hpp:296   kUpdateTablePieces: one ring slot of 32-byte pieces
-RING_SLOTS = 32                  # ec_core.hpp:352   UploadRing::kSlots
-CHUNK = 16                       # update_plan.hpp:53 update::kChunk
-TILE = 256 * CHUNK               # update_plan.hpp:54 update::kTileBytes
+TABLE_CHUNK = 256 * 1024 // 32   # update_plan.hpp   update::kTablePieces: one ring slot of 32-byte pieces
+RING_SLOTS = 32                  # ec_core.hpp        UploadRing::kSlots
+CHUNK = 16                       # piece_plan.hpp     piece::kChunk
+TILE = 256 * CHUNK               # piece_plan.hpp     piece::kTileBytes
 
 
 def _piece_lens(offset, n):
-    """update_plan.hpp split(): a byte-granular head up to the next multiple
+    """piece_plan.hpp split(): a byte-granular head up to the next multiple
     of 16, the whole chunks (one piece: every length here is far below
     kMaxPieceBytes), a byte-granular tail."""
     out = []

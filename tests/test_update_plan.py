@@ -185,6 +185,30 @@ def test_fuzz_20000_updates(check, seed):
     assert 2 <= int(nrounds) <= 8 and int(npieces) >= 20000
 
 
+def chunks(check, updates, **kw):
+    """-> the sizes of the table chunks the planned pieces travel in."""
+    args = dict(nblocks=1, k=4, shard_len=1 << 20, src_bytes=1 << 40)
+    args.update(kw)
+    text = "chunks {nblocks} {k} {shard_len} {src_bytes} ".format(**args) + f"{len(updates)}\n" + "".join(
+        "%d %d %d %d %d\n" % u for u in updates)
+    out = check(text)[0].split()
+    assert out[0] == "ok", out
+    return [int(x) for x in out[1:]]
+
+
+def test_table_chunks(check):
+    """A chunk holds one ring slot of 32-byte entries (8192) and fewer than 2^31
+    tiles: 8192 pieces of the largest size are exactly 2^31 tiles, one too many
+    for a launch's grid, so the last piece takes a chunk of its own."""
+    table, maxpiece = 256 * 1024 // 32, 1 << 30
+    assert table * (maxpiece // TILE) == 1 << 31
+    big = dict(nblocks=table + 1, shard_len=maxpiece, src_bytes=maxpiece)
+    assert chunks(check, [(b, 0, 0, maxpiece, 0) for b in range(table)], **big) == [table - 1, 1]
+    assert chunks(check, [(b, 0, 0, 4096, 0) for b in range(table)], **big) == [table]
+    assert chunks(check, [(b, 0, 0, 4096, 0) for b in range(table + 1)], **big) == [table, 1]
+    assert chunks(check, [], nblocks=0) == []
+
+
 def test_tile_search(check):
     t0 = [0, 1, 2, 10, 11, 300]
     for tile, want in [(0, 0), (1, 1), (2, 2), (9, 2), (10, 3), (11, 4), (299, 4), (300, 5), (301, 5)]:

@@ -20,6 +20,7 @@
 #include <random>
 #include <vector>
 
+#include "plan_check.hpp"
 #include "read_plan.hpp"
 
 namespace rd = shmr::read;
@@ -28,7 +29,7 @@ namespace rd = shmr::read;
 static std::vector<uint32_t> tile_prefixes(const std::vector<rd::Piece>& ps) {
     std::vector<uint32_t> t0(ps.size());
     for (size_t c0 = 0; c0 < ps.size();) {
-        const size_t cnt = rd::chunk_pieces(ps, c0);
+        const size_t cnt = rd::chunk_pieces<rd::DevPiece>(ps, c0);
         uint32_t tiles = 0;
         for (size_t i = 0; i < cnt; ++i) {
             t0[c0 + i] = tiles;
@@ -39,29 +40,16 @@ static std::vector<uint32_t> tile_prefixes(const std::vector<rd::Piece>& ps) {
     return t0;
 }
 
-// What every plan must satisfy: the pieces of a request tile it exactly, in
-// order, source and destination alike; vector pieces are whole chunks on chunk
-// columns; every tile of a chunk is found in its own piece.
+// What every plan must satisfy: the pieces of a request tile it exactly, source
+// and destination alike (plan_check.hpp), in list order; every tile of a chunk
+// is found in its own piece.
 static const char* check(const std::vector<shmr_ec_read>& r, const std::vector<rd::Piece>& ps) {
-    size_t at = 0;
-    for (size_t i = 0; i < r.size(); ++i) {
-        uint64_t col = r[i].offset, dst = r[i].dst_offset;
-        for (; at < ps.size() && ps[at].read == i; ++at) {
-            const rd::Piece& p = ps[at];
-            if (p.col != col || p.dst != dst || p.len == 0) return "pieces do not tile the request";
-            if (p.block != r[i].block || p.shard != r[i].shard) return "piece fields";
-            if (p.vec ? (p.col % rd::kChunk || p.len % rd::kChunk || p.len > rd::kMaxPieceBytes)
-                      : p.len >= rd::kChunk || p.col / rd::kChunk != (p.col + p.len - 1) / rd::kChunk)
-                return "piece shape";
-            col += p.len;
-            dst += p.len;
-        }
-        if (col != r[i].offset + r[i].len) return "pieces do not cover the request";
-    }
-    if (at != ps.size()) return "piece of no request";
+    if (const char* bad = plan_check::check_tiling(r, &shmr_ec_read::dst_offset, ps, nullptr)) return bad;
+    for (size_t i = 1; i < ps.size(); ++i)
+        if (ps[i - 1].request > ps[i].request) return "pieces not in list order";
     const std::vector<uint32_t> t0 = tile_prefixes(ps);
     for (size_t c0 = 0; c0 < ps.size();) {
-        const size_t cnt = rd::chunk_pieces(ps, c0);
+        const size_t cnt = rd::chunk_pieces<rd::DevPiece>(ps, c0);
         if (cnt == 0 || cnt > rd::kTablePieces) return "chunk size";
         for (size_t i = 0; i < cnt; ++i) {
             const uint32_t first = t0[c0 + i], last = first + rd::piece_tiles(ps[c0 + i].len) - 1;
@@ -86,10 +74,7 @@ int main() {
             if (std::scanf("%" SCNu64 " %u %" SCNu64 " %" SCNu64 " %" SCNu64, &nblocks, &k, &shard_len, &dst_bytes, &n) != 5)
                 return 2;
             std::vector<shmr_ec_read> r(n);
-            for (auto& x : r)
-                if (std::scanf("%" SCNu32 " %" SCNu32 " %" SCNu64 " %" SCNu64 " %" SCNu64, &x.block, &x.shard, &x.offset,
-                               &x.len, &x.dst_offset) != 5)
-                    return 2;
+            if (!plan_check::scan_requests(&r, &shmr_ec_read::dst_offset)) return 2;
             std::vector<rd::Piece> ps;
             if (!rd::plan(r.data(), r.size(), nblocks, k, shard_len, dst_bytes, &ps)) {
                 std::printf("invalid\n");
@@ -103,8 +88,8 @@ int main() {
             const std::vector<uint32_t> t0 = tile_prefixes(ps);
             for (size_t i = 0; i < ps.size(); ++i) {
                 const rd::Piece& p = ps[i];
-                std::printf("%" PRIu64 " %u %u %" PRIu64 " %u %" PRIu64 " %d %u %u\n", p.read, p.block, p.shard, p.col, p.len,
-                            p.dst, int(p.vec), rd::piece_tiles(p.len), t0[i]);
+                std::printf("%" PRIu64 " %u %u %" PRIu64 " %u %" PRIu64 " %d %u %u\n", p.request, p.block, p.shard, p.col,
+                            p.len, p.flat, int(p.vec), rd::piece_tiles(p.len), t0[i]);
             }
         } else if (!std::strcmp(cmd, "fuzz")) {
             uint64_t seed, n, nblocks, shard_len;
@@ -137,13 +122,7 @@ int main() {
             if (const char* bad = check(r, ps)) std::printf("bad %s\n", bad);
             else std::printf("ok %zu %u\n", ps.size(), rd::count_chunks(ps));
         } else if (!std::strcmp(cmd, "find")) {
-            unsigned n, tile;
-            if (std::scanf("%u", &n) != 1 || n == 0) return 2;
-            std::vector<uint32_t> t0(n);
-            for (auto& x : t0)
-                if (std::scanf("%" SCNu32, &x) != 1) return 2;
-            if (std::scanf("%u", &tile) != 1) return 2;
-            std::printf("%u\n", rd::find_piece([&](uint32_t i) { return t0[i]; }, n, tile));
+            if (!plan_check::run_find()) return 2;
         } else {
             return 2;
         }

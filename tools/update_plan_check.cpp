@@ -5,6 +5,9 @@
 //   "plan nblocks k shard_len src_bytes n" + n x "block shard offset len src_offset"
 //           -> "invalid", or "ok nrounds npieces", a line of the n rounds, then
 //              per piece "update block shard col len src round vec tiles"
+//   "chunks nblocks k shard_len src_bytes n" + the n updates as for "plan"
+//           -> "invalid", or "ok" and the sizes of the table chunks the pieces
+//              travel in (piece::chunk_pieces), in order
 //   "fuzz seed n nblocks k shard_len"
 //           -> a seeded list of n updates valid by construction (distinct
 //              (block, shard, 64-column slot), random sub-range of the slot),
@@ -21,35 +24,21 @@
 #include <tuple>
 #include <vector>
 
+#include "plan_check.hpp"
 #include "update_plan.hpp"
 
 namespace up = shmr::update;
 
-// What every plan must satisfy: the pieces of an update tile it exactly, in
-// order; vector pieces are whole chunks on chunk columns; no round holds two
-// pieces of a block whose footprints (column ranges) intersect.
+// What every plan must satisfy: the pieces of an update tile it exactly
+// (plan_check.hpp), they come in round order, and no round holds two pieces of
+// a block whose footprints (column ranges) intersect.
 static const char* check(const std::vector<shmr_ec_update>& u, const up::Plan& pl) {
-    std::vector<std::vector<const up::Piece*>> of(u.size());
-    for (const up::Piece& p : pl.pieces) {
-        if (p.update >= u.size()) return "piece of no update";
-        of[p.update].push_back(&p);
-    }
     for (size_t i = 1; i < pl.pieces.size(); ++i)
         if (pl.pieces[i - 1].round > pl.pieces[i].round) return "pieces not in round order";
-    for (size_t i = 0; i < u.size(); ++i) {
-        uint64_t col = u[i].offset, src = u[i].src_offset;
+    for (size_t i = 0; i < u.size(); ++i)
         if (pl.round_of[i] >= pl.nrounds) return "round out of range";
-        for (const up::Piece* p : of[i]) {
-            if (p->col != col || p->src != src || p->len == 0) return "pieces do not tile the update";
-            if (p->block != u[i].block || p->shard != u[i].shard || p->round != pl.round_of[i]) return "piece fields";
-            if (p->vec ? (p->col % up::kChunk || p->len % up::kChunk || p->len > up::kMaxPieceBytes)
-                       : p->len >= up::kChunk || p->col / up::kChunk != (p->col + p->len - 1) / up::kChunk)
-                return "piece shape";
-            col += p->len;
-            src += p->len;
-        }
-        if (col != u[i].offset + u[i].len) return "pieces do not cover the update";
-    }
+    if (const char* bad = plan_check::check_tiling(u, &shmr_ec_update::src_offset, pl.pieces, pl.round_of.data()))
+        return bad;
     // per (block, round): ranges sorted by first column must not intersect
     std::map<std::pair<uint32_t, uint32_t>, std::vector<std::pair<uint64_t, uint64_t>>> fp;
     for (const up::Piece& p : pl.pieces) fp[{p.block, p.round}].push_back({p.col, p.col + p.len});
@@ -67,16 +56,13 @@ int main() {
         if (!std::strcmp(cmd, "rule")) {
             std::printf("edges %s\nchunk %u tile %u maxpiece %" PRIu64 "\n", up::kByteExactEdges ? "byte-exact" : "widened",
                         up::kChunk, up::kTileBytes, up::kMaxPieceBytes);
-        } else if (!std::strcmp(cmd, "plan")) {
+        } else if (!std::strcmp(cmd, "plan") || !std::strcmp(cmd, "chunks")) {
             uint64_t nblocks, shard_len, src_bytes, n;
             unsigned k;
             if (std::scanf("%" SCNu64 " %u %" SCNu64 " %" SCNu64 " %" SCNu64, &nblocks, &k, &shard_len, &src_bytes, &n) != 5)
                 return 2;
             std::vector<shmr_ec_update> u(n);
-            for (auto& x : u)
-                if (std::scanf("%" SCNu32 " %" SCNu32 " %" SCNu64 " %" SCNu64 " %" SCNu64, &x.block, &x.shard, &x.offset,
-                               &x.len, &x.src_offset) != 5)
-                    return 2;
+            if (!plan_check::scan_requests(&u, &shmr_ec_update::src_offset)) return 2;
             up::Plan pl;
             if (!up::plan(u.data(), u.size(), nblocks, k, shard_len, src_bytes, &pl)) {
                 std::printf("invalid\n");
@@ -86,12 +72,18 @@ int main() {
                 std::printf("bad %s\n", bad);
                 continue;
             }
+            if (!std::strcmp(cmd, "chunks")) {
+                std::printf("ok");
+                for (size_t c : plan_check::chunk_sizes<up::DevPiece>(pl.pieces)) std::printf(" %zu", c);
+                std::printf("\n");
+                continue;
+            }
             std::printf("ok %u %zu\n", pl.nrounds, pl.pieces.size());
             for (size_t i = 0; i < n; ++i) std::printf("%u%c", pl.round_of[i], i + 1 == n ? '\n' : ' ');
             if (!n) std::printf("\n");
             for (const up::Piece& p : pl.pieces)
-                std::printf("%" PRIu64 " %u %u %" PRIu64 " %u %" PRIu64 " %u %d %u\n", p.update, p.block, p.shard, p.col, p.len,
-                            p.src, p.round, int(p.vec), up::piece_tiles(p.len));
+                std::printf("%" PRIu64 " %u %u %" PRIu64 " %u %" PRIu64 " %u %d %u\n", p.request, p.block, p.shard, p.col,
+                            p.len, p.flat, p.round, int(p.vec), up::piece_tiles(p.len));
         } else if (!std::strcmp(cmd, "fuzz")) {
             uint64_t seed, n, nblocks, shard_len;
             unsigned k;
@@ -119,13 +111,7 @@ int main() {
             if (const char* bad = check(u, pl)) std::printf("bad %s\n", bad);
             else std::printf("ok %u %zu\n", pl.nrounds, pl.pieces.size());
         } else if (!std::strcmp(cmd, "find")) {
-            unsigned n, tile;
-            if (std::scanf("%u", &n) != 1 || n == 0) return 2;
-            std::vector<uint32_t> t0(n);
-            for (auto& x : t0)
-                if (std::scanf("%" SCNu32, &x) != 1) return 2;
-            if (std::scanf("%u", &tile) != 1) return 2;
-            std::printf("%u\n", up::find_piece([&](uint32_t i) { return t0[i]; }, n, tile));
+            if (!plan_check::run_find()) return 2;
         } else {
             return 2;
         }
