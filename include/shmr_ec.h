@@ -337,6 +337,88 @@ int shmr_ec_scrub_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pi
                             size_t parity_block_pitch, size_t nblocks, size_t shard_len,
                             int32_t* located_host, uint64_t* counts, int device, void* stream);
 
+/* ---- scrub, parity >= 4: locate and repair two damaged shards per block ------ *
+ * The calls above stop at one damaged shard per block.  A code with
+ * parity >= 4 has distance >= 5 and determines two: with G the first group of
+ * four parity rows and H' = [C[0:4] | I_4], damage in shards e and f leaves
+ * s_G in span(H'_e, H'_f) in every column, and no other pair is consistent
+ * with every column once each of the two is hit somewhere.  Per block two
+ * answers, located[2b] and located[2b + 1]:
+ *   - (shmr_ec_locate_batch_dev's answer, SHMR_EC_LOCATE_CLEAN) wherever that
+ *     answer is not SHMR_EC_LOCATE_NONE: clean blocks and single shards are
+ *     exactly locate's;
+ *   - (lower index, higher index) of the one pair of shards whose damage
+ *     explains the block;
+ *   - (SHMR_EC_LOCATE_NONE, SHMR_EC_LOCATE_NONE): no single shard and no pair.
+ * What the answer promises:
+ *   - the located pair is exact for damage in two of the data + 4 shards the
+ *     group sees (the data shards and parity shards 0 .. 3);
+ *   - parity == 4 (distance 5): damage in three shards can pass for damage in
+ *     two, as with any distance-5 code;
+ *   - parity >= 5: that case is caught by shmr_ec_scrub_pair_batch_dev's
+ *     closing verify;
+ *   - parity rows at and beyond 4 are used only through the verify word, as in
+ *     locate: a block with a row there that does not differ has no pair with a
+ *     data shard in it, and a data shard plus a parity shard beyond the group
+ *     is still reported as the data shard alone (and demoted by the scrub's
+ *     closing verify).
+ * Needs 4 <= parity <= 32 and data <= 29 (the pair tables of a larger code do
+ * not fit the 64 KiB of LDS they are staged in); INVALID_ARGUMENT otherwise. */
+
+/* Bytes of device scratch shmr_ec_locate_pair_batch_dev needs for nblocks
+ * blocks (positive, never shrinking as nblocks grows, at least
+ * shmr_ec_locate_work_size: locate's scratch, the pair bitmaps, a worklist and
+ * its counter); 0 for a codec it refuses. */
+size_t shmr_ec_locate_pair_work_size(const shmr_ec_t* rs, size_t nblocks);
+
+/* Verify, locate, and locate pairs in nblocks blocks: arguments as
+ * shmr_ec_locate_batch_dev, except that d_located is nblocks * 2 int32 (device)
+ * and d_work is work_bytes >= shmr_ec_locate_pair_work_size(rs, nblocks).
+ * d_mismatch receives verify's words unchanged.  Read-only over the shards:
+ * behind locate's kernels, a kernel that lists the blocks no single shard
+ * explains and one that reads the data and first-group parity of the listed
+ * blocks (one word per workgroup when none is listed).  Stream-ordered, no
+ * allocation and no host readback.  NOT capturable, as
+ * shmr_ec_locate_batch_dev: a capturing `stream`, a small d_work and an
+ * unsupported codec are refused with INVALID_ARGUMENT and nothing is
+ * enqueued. */
+int shmr_ec_locate_pair_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_shard_pitch,
+                                  size_t data_block_pitch, const uint8_t* d_parity,
+                                  size_t parity_shard_pitch, size_t parity_block_pitch,
+                                  size_t nblocks, size_t shard_len, uint32_t* d_mismatch,
+                                  int32_t* d_located, void* d_work, size_t work_bytes,
+                                  int device, void* stream);
+
+/* The whole scrub for up to two damaged shards per block, blocking (NOT
+ * stream-ordered, NOT capturable), arguments as shmr_ec_scrub_batch_dev:
+ * locate pairs; copy the answers to the host; rebuild the one or two located
+ * shards of each such block in place through shmr_ec_reconstruct_ptrs_dev's
+ * path (present = every shard but those); verify again, and demote a rebuilt
+ * block that still differs to (SHMR_EC_LOCATE_NONE, SHMR_EC_LOCATE_NONE) (its
+ * located shards have been rewritten).  Blocks reported
+ * SHMR_EC_LOCATE_NONE are not written at all.
+ * located_host: nblocks * 2 int32 of HOST memory, or NULL.  counts (HOST, 4
+ * entries): blocks clean, repaired in one shard, repaired in two, not
+ * repairable; written (zeroed first) only once the arguments and the device
+ * have been accepted, so a refused call leaves them alone. */
+int shmr_ec_scrub_pair_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pitch,
+                                 size_t data_block_pitch, uint8_t* d_parity,
+                                 size_t parity_shard_pitch, size_t parity_block_pitch,
+                                 size_t nblocks, size_t shard_len, int32_t* located_host,
+                                 uint64_t* counts, int device, void* stream);
+
+/* Host only; for tests and tools (as shmr_ec_locate_checked_plan): the
+ * coefficients the pair kernel multiplies by, in pair-index order.  The
+ * candidates of a block are the data-data pairs (a, b), a < b, in
+ * lexicographic order, then the data-parity pairs (a, data + r), r < 4, at
+ * a * 4 + r; *npairs = data (data - 1) / 2 + 4 data of them.  coeffs: four
+ * bytes per data-data pair (s_2 == c0 s_0 ^ c1 s_1, s_3 == c2 s_0 ^ c3 s_1),
+ * then two per data-parity pair (the ratios of the two rows other than r and
+ * the base row against the base row, ascending row; the base row is row 0,
+ * or row 1 for r == 0): 2 data (data - 1) + 8 data bytes.  coeffs_len below
+ * that, or a codec the pair calls refuse: INVALID_ARGUMENT. */
+int shmr_ec_locate_pair_plan(shmr_ec_t* rs, uint8_t* coeffs, size_t coeffs_len, uint32_t* npairs);
+
 /* ---- parity delta update: writes into device-resident blocks ---------------- *
  * Changes part of a resident block and keeps its parity valid without
  * re-encoding it.  The code is linear: for every update,

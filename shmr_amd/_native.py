@@ -64,6 +64,14 @@ SIGNATURES = [
     ("shmr_ec_scrub_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _sz, _sz,
       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_locate_pair_work_size", _sz, [ctypes.c_void_p, _sz]),
+    ("shmr_ec_locate_pair_batch_dev", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _sz, _sz, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_scrub_pair_batch_dev", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _sz, _sz,
+      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_locate_pair_plan", ctypes.c_int, [ctypes.c_void_p, _u8p, _sz, ctypes.POINTER(ctypes.c_uint32)]),
     ("shmr_ec_update_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _sz, _sz, ctypes.c_void_p, _sz,
       ctypes.c_void_p, _sz, ctypes.c_int, ctypes.c_void_p]),

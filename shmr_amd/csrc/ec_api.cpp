@@ -1030,6 +1030,116 @@ int shmr_ec_scrub_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pi
     });
 }
 
+// ---- scrub, parity >= 4: locate and repair two damaged shards per block ---------------
+size_t shmr_ec_locate_pair_work_size(const shmr_ec_t* rs, size_t nblocks) {
+    return rs && rs->codec->locate_pair_plan() ? core::locate_pair_work_bytes(*rs->codec, nblocks) : 0;
+}
+
+int shmr_ec_locate_pair_plan(shmr_ec_t* rs, uint8_t* coeffs, size_t coeffs_len, uint32_t* npairs) {
+    return guarded_light([&]() -> int {
+        if (!rs || !coeffs || !npairs) return SHMR_EC_INVALID_ARGUMENT;
+        const auto pp = rs->codec->locate_pair_plan();
+        if (!pp || coeffs_len < pp->rows.d.size()) return SHMR_EC_INVALID_ARGUMENT;
+        std::memcpy(coeffs, pp->rows.d.data(), pp->rows.d.size());
+        *npairs = shmr::locate::pair_count(rs->codec->k());
+        return SHMR_EC_OK;
+    });
+}
+
+int shmr_ec_locate_pair_batch_dev(shmr_ec_t* rs, const uint8_t* d_data, size_t data_shard_pitch,
+                                  size_t data_block_pitch, const uint8_t* d_parity, size_t parity_shard_pitch,
+                                  size_t parity_block_pitch, size_t nblocks, size_t shard_len, uint32_t* d_mismatch,
+                                  int32_t* d_located, void* d_work, size_t work_bytes, int device, void* stream) {
+    return guarded([&]() -> int {
+        if (!rs || !rs->codec->locate_pair_plan()) return SHMR_EC_INVALID_ARGUMENT;
+        Codec& c = *rs->codec;
+        const bool given = d_data && d_parity && words_given(d_mismatch) && words_given(d_located) &&
+                           words_given(d_work) && work_bytes >= core::locate_pair_work_bytes(c, nblocks);
+        return batch_dev(nblocks, shard_len, device, [&] { return arg_ok(given); }, [&] {
+            const core::Layout L = batch_layout(c, d_data, data_shard_pitch, data_block_pitch, d_parity,
+                                                parity_shard_pitch, parity_block_pitch);
+            return core::locate_pair_on_device(c, device, L, nblocks, shard_len, d_mismatch, d_located,
+                                               static_cast<uint8_t*>(d_work), static_cast<hipStream_t>(stream));
+        });
+    });
+}
+
+int shmr_ec_scrub_pair_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pitch, size_t data_block_pitch,
+                                 uint8_t* d_parity, size_t parity_shard_pitch, size_t parity_block_pitch,
+                                 size_t nblocks, size_t shard_len, int32_t* located_host, uint64_t* counts, int device,
+                                 void* stream_) {
+    return guarded([&]() -> int {
+        hipStream_t stream = static_cast<hipStream_t>(stream_);
+        if (!rs || !counts || !rs->codec->locate_pair_plan()) return SHMR_EC_INVALID_ARGUMENT;
+        // (an empty batch is accepted)
+        if (nblocks == 0) std::fill(counts, counts + 4, uint64_t(0));
+        Codec& c = *rs->codec;
+        return batch_dev(nblocks, shard_len, device, [&] { return arg_ok(d_data && d_parity); }, [&]() -> int {
+            int rc = core::refuse_capture(device, stream);   // it waits for its own results
+            if (rc) return rc;
+            std::fill(counts, counts + 4, uint64_t(0));
+            const core::Layout L = batch_layout(c, d_data, data_shard_pitch, data_block_pitch, d_parity,
+                                                parity_shard_pitch, parity_block_pitch);
+            // pooled scratch (grown without a free): the words, the answers, the location's own
+            const size_t words_bytes = size_t(core::round_up(nblocks * sizeof(uint32_t), 256));
+            core::StagingLease lease;
+            lease.s = core::StagingPool::get().acquire(
+                device, 3 * words_bytes + core::locate_pair_work_bytes(c, nblocks), &rc);
+            if (!lease.s) return rc;
+            uint32_t* d_words = reinterpret_cast<uint32_t*>(lease.s->dbuf);
+            int32_t* d_located = reinterpret_cast<int32_t*>(lease.s->dbuf + words_bytes);
+            uint8_t* d_work = lease.s->dbuf + 3 * words_bytes;
+            // (a failure below still waits: the scratch goes back to the pool idle)
+            auto fetch = [&](void* dst, const void* src, size_t n) -> int {
+                const hipError_t e = hipMemcpyAsync(dst, src, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+                const hipError_t w = core::sync_stream(stream);
+                return e == hipSuccess && w == hipSuccess ? SHMR_EC_OK : SHMR_EC_DEVICE_ERROR;
+            };
+            std::vector<int32_t> own;
+            int32_t* located = located_host;
+            if (!located) {
+                own.resize(2 * nblocks);
+                located = own.data();
+            }
+            rc = core::locate_pair_on_device(c, device, L, nblocks, shard_len, d_words, d_located, d_work, stream);
+            const int frc = fetch(located, d_located, 2 * nblocks);
+            if (rc || frc) return rc ? rc : frc;
+            std::vector<size_t> hit;
+            for (size_t b = 0; b < nblocks; ++b) {
+                if (located[2 * b] >= 0) hit.push_back(b);
+                else ++counts[located[2 * b] == SHMR_EC_LOCATE_CLEAN ? 0 : 3];
+            }
+            if (hit.empty()) return SHMR_EC_OK;
+            // the located shards of every such block, rebuilt from the block's other shards
+            const unsigned k = c.k(), t = k + c.p();
+            std::vector<uint64_t> tab(hit.size() * t);
+            std::vector<uint8_t> present(hit.size() * t, 1);
+            for (size_t i = 0; i < hit.size(); ++i) {
+                const size_t b = hit[i];
+                for (unsigned s = 0; s < t; ++s)
+                    tab[i * t + s] = s < k ? uint64_t(uintptr_t(d_data + b * data_block_pitch + s * data_shard_pitch))
+                                           : uint64_t(uintptr_t(d_parity + b * parity_block_pitch +
+                                                                (s - k) * parity_shard_pitch));
+                present[i * t + size_t(located[2 * b])] = 0;
+                if (located[2 * b + 1] >= 0) present[i * t + size_t(located[2 * b + 1])] = 0;
+            }
+            rc = core::ptrs_launch(c, tab.data(), present.data(), hit.size(), shard_len, false, device, stream,
+                                   core::kDecode, false, false);
+            // the closing verify: damage beyond what the location looked at shows here
+            if (rc == SHMR_EC_OK) rc = core::verify_on_device(c, device, L, nblocks, shard_len, d_words, stream);
+            std::vector<uint32_t> words(nblocks);
+            const int wrc = fetch(words.data(), d_words, nblocks);
+            if (rc || wrc) return rc ? rc : wrc;
+            for (size_t b : hit) {
+                const bool two = located[2 * b + 1] >= 0;
+                if (words[b] != 0) located[2 * b] = located[2 * b + 1] = SHMR_EC_LOCATE_NONE;
+                ++counts[words[b] != 0 ? 3 : (two ? 2 : 1)];
+            }
+            return SHMR_EC_OK;
+        });
+    });
+}
+
 // ---- parity delta update: writes into device-resident blocks -------------------------
 int shmr_ec_update_batch_dev(shmr_ec_t* rs, uint8_t* d_data, size_t data_shard_pitch, size_t data_block_pitch,
                              uint8_t* d_parity, size_t parity_shard_pitch, size_t parity_block_pitch, size_t nblocks,

@@ -84,6 +84,10 @@ std::atomic<int> g_pattern_launches{0};
 // 0 = the table kernels instead (measured faster: profiles/r06 s1, s3, s14,
 // ptrs_ab pool_holed vs pool_holed_tab), 1 = the strided kernels over the list
 std::atomic<int> g_lattice_list{0};
+// Two-shard location: 1 = a wave reads a group's pair bitmap word before it
+// tests the group and leaves out the candidates that are already cleared, 0 =
+// it tests every candidate in every damaged tile (same answers)
+std::atomic<int> g_pair_skip{1};
 
 // The launch policy itself is kern::policy_variant (gf_apply.hpp): constexpr,
 // so the product library compiles exactly the kernels it can select.  Its
@@ -186,6 +190,7 @@ const K kKnobs[] = {
       nullptr, false},
     process_knob("pattern_launches", &g_pattern_launches, 0, any(), true),
     process_knob("lattice_list", &g_lattice_list, 0, among(0, 1)),
+    process_knob("pair_skip", &g_pair_skip, 1, among(0, 1)),
     // tools build only: the product build answers OK for 0 or -2 and INVALID_ARGUMENT for anything else
     knobs::tools_only(process_knob("slots_list", &g_slots_list, 0, among(0, 1))),
     knobs::tools_only(process_knob("alias_devices", &g_alias_devices, 0, range(0, 32))),   // (see ec_core.hpp)
@@ -1248,6 +1253,66 @@ int locate_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint6
     });
     if (rc) return rc;
     SHMR_HIP_TRY(kern::launch_locate_resolve(d_mismatch, d_cand, d_located, nblocks, plan.k, plan.m, stream));
+    return SHMR_EC_OK;
+}
+
+// ===========================================================================
+// Two-shard location (p >= 4).  The location above into scratch (the single
+// answers); the pair bitmaps preset and the worklist counter zeroed; the select
+// kernel; the pair kernel over the worklist, split as a verify's launches of
+// the first row group (4 KiB tiles); the pair resolve kernel.  One more launch
+// group is counted.
+// ===========================================================================
+namespace {
+// d_work of a pair location: locate's bitmaps, the single answers, the pair
+// bitmaps, the worklist, its counter -- each from a 256-byte boundary.
+struct PairWork {
+    size_t single, pairs, list, count, bytes;
+};
+PairWork pair_work(const Codec& c, uint64_t nblocks) {
+    const uint64_t n = std::max<uint64_t>(nblocks, 1);
+    PairWork w;
+    w.single = locate_work_bytes(c, nblocks);
+    w.pairs = w.single + size_t(round_up(n * sizeof(int32_t), 256));
+    w.list = w.pairs + size_t(round_up(n * locate::pair_bitmap_words(c.k()) * sizeof(uint32_t), 256));
+    w.count = w.list + size_t(round_up(n * sizeof(uint32_t), 256));
+    w.bytes = w.count + 256;
+    return w;
+}
+}  // namespace
+
+size_t locate_pair_work_bytes(const Codec& c, uint64_t nblocks) { return pair_work(c, nblocks).bytes; }
+
+int locate_pair_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint64_t len, uint32_t* d_mismatch,
+                          int32_t* d_located, uint8_t* d_work, hipStream_t stream) {
+    const std::shared_ptr<Plan> pplan = c.locate_pair_plan();
+    if (!pplan || nblocks > 0xffffffffull) return SHMR_EC_INVALID_ARGUMENT;   // (the worklist is 32-bit)
+    const PairWork w = pair_work(c, nblocks);
+    int32_t* d_single = reinterpret_cast<int32_t*>(d_work + w.single);
+    uint32_t* d_pairs = reinterpret_cast<uint32_t*>(d_work + w.pairs);
+    uint32_t* d_list = reinterpret_cast<uint32_t*>(d_work + w.list);
+    uint32_t* d_count = reinterpret_cast<uint32_t*>(d_work + w.count);
+    // (a capturing stream is refused in there, before anything is enqueued)
+    int rc = locate_on_device(c, dev, L, nblocks, len, d_mismatch, d_single, reinterpret_cast<uint32_t*>(d_work),
+                              stream);
+    if (rc || nblocks == 0) return rc;
+    Plan& plan = *c.encode_plan();
+    SHMR_HIP_TRY(kern::launch_locate_pair_preset(d_pairs, d_count, nblocks, plan.k, stream));
+    SHMR_HIP_TRY(kern::launch_locate_pair_select(d_mismatch, d_single, d_list, d_count, nblocks, plan.m, stream));
+    const uint8_t *dplan = nullptr, *dpair = nullptr;
+    rc = plan_on_device(plan, dev, stream, false, &dplan);
+    if (rc) return rc;
+    rc = plan_on_device(*pplan, dev, stream, false, &dpair);
+    if (rc) return rc;
+    const bool skip = g_pair_skip.load(std::memory_order_relaxed) != 0;
+    kern::ApplyArgs a = batch_args(L, plan, dplan, len, nblocks);
+    rc = compare_groups(dev, L, a, locate::rows_used(plan.m), len, tile_4k, [&](uint32_t, uint32_t, int mode, int) {
+        return kern::launch_locate_pair(a, dpair + plan_tab_off(pplan->k, pplan->m), d_list, d_count, d_pairs, mode,
+                                        skip, stream);
+    });
+    if (rc) return rc;
+    SHMR_HIP_TRY(kern::launch_locate_pair_resolve(d_mismatch, d_single, d_pairs, d_located, nblocks, plan.k, plan.m,
+                                                  stream));
     return SHMR_EC_OK;
 }
 

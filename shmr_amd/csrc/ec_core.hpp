@@ -290,6 +290,16 @@ int verify_chunks(unsigned rows);
 size_t locate_work_bytes(const Codec& c, uint64_t nblocks);
 int locate_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint64_t len, uint32_t* d_mismatch,
                      int32_t* d_located, uint32_t* d_cand, hipStream_t stream);
+// Two-shard location, for codecs with a pair plan (4 <= p <= 32, k <=
+// locate::pair_max_data, else INVALID_ARGUMENT with nothing enqueued):
+// locate_on_device into scratch, then d_located[2 b], [2 b + 1] =
+// locate::resolve_pair of block b's word, single answer and pair bitmap
+// (locate_plan.hpp).  d_work: locate_pair_work_bytes(c, nblocks) bytes of
+// device scratch, 4-byte aligned.  Stream order, capture and what is written as
+// locate_on_device.
+size_t locate_pair_work_bytes(const Codec& c, uint64_t nblocks);
+int locate_pair_on_device(Codec& c, int dev, const Layout& L, uint64_t nblocks, uint64_t len, uint32_t* d_mismatch,
+                          int32_t* d_located, uint8_t* d_work, hipStream_t stream);
 // Parity delta update (shmr_ec_update_batch_dev): the planned pieces `up`
 // (update_plan.hpp, validated by the caller) applied to blocks laid out per
 // `L` as for encode_on_device (L.in_base: the data, written here too), the new

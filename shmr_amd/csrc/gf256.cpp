@@ -156,6 +156,15 @@ Codec::Codec(unsigned k, unsigned p) : k_(k), p_(p), matrix_(build_matrix(k, k +
     lp->in_idx = plan->in_idx;
     for (unsigned r = 1; r < R; ++r) lp->out_idx.push_back(uint16_t(k + r));   // (unused: nothing is stored)
     locate_plan_ = lp;
+    if (!locate::pair_supported(k, p)) return;
+    auto pp = std::make_shared<Plan>();
+    pp->k = 1;
+    pp->m = locate::pair_coeff_count(k);
+    pp->rows = Matrix(pp->m, 1);
+    if (!locate::pair_coeffs(matrix_.row(k), k, mul, div, pp->rows.d.data())) return;
+    pp->in_idx.push_back(0);
+    pp->out_idx.assign(pp->m, 0);   // (unused: nothing is stored)
+    locate_pair_plan_ = pp;
 }
 
 // Device plan images live in the per-device arenas of ec_core (process

@@ -101,6 +101,12 @@ public:
     // the shape of an encode plan: k inputs, min(p, 4) - 1 rows, row r-1 entry j
     // = C[r][j] / C[0][j].  Null when the codec cannot locate (p < 2 or p > 32).
     std::shared_ptr<Plan> locate_plan() const { return locate_plan_; }
+    // The coefficients of two-shard location (locate_plan.hpp pair_coeffs) as a
+    // plan of one input and pair_coeff_count(k) rows: rows.d holds the
+    // coefficient bytes in pair-index order, the device image their perm
+    // tables back to back.  Null when the codec cannot locate pairs
+    // (locate_plan.hpp pair_supported: 4 <= p <= 32, k <= pair_max_data).
+    std::shared_ptr<Plan> locate_pair_plan() const { return locate_pair_plan_; }
 
     // Crate get_data_decode_matrix: inverse of the rows of `valid`,
     // LRU-cached (capacity 254) keyed by `invalid`.
@@ -140,6 +146,7 @@ private:
     Matrix matrix_;
     std::shared_ptr<Plan> encode_plan_;
     std::shared_ptr<Plan> locate_plan_;
+    std::shared_ptr<Plan> locate_pair_plan_;
 
     std::mutex mu_;
     // LRU of decode matrices (crate semantics), key = invalid indices.

@@ -358,6 +358,27 @@ hipError_t launch_locate_checked_resolve(const ApplyArgs& a, const uint32_t* mis
                                          int32_t* located, const uint16_t* idx, unsigned s, uint32_t row_mask,
                                          hipStream_t stream);
 
+// The two-shard location kernels (gf_locate.hip; shmr_ec_locate_pair_batch_dev),
+// behind launch_locate_resolve of the same blocks (single[b] its answers), for
+// codecs of locate::pair_supported; words = locate::pair_bitmap_words(k).
+// Not part of kernel_inventory.
+// pairs[0 .. nblk * words) = all ones, *count = 0.
+hipError_t launch_locate_pair_preset(uint32_t* pairs, uint32_t* count, uint64_t nblk, unsigned k, hipStream_t stream);
+// Appends every block b < nblk of locate::pair_listed(mismatch[b], single[b], p)
+// to list[] (nblk entries, any order) and counts them in *count.
+hipError_t launch_locate_pair_select(const uint32_t* mismatch, const int32_t* single, uint32_t* list, uint32_t* count,
+                                     uint64_t nblk, unsigned p, hipStream_t stream);
+// `a` as for launch_verify of the first row group (a.row0 = 0, 4 rows) over the
+// whole batch; ptab the tables of the codec's pair plan.  For each listed
+// block, clears the bit of every candidate pair that this launch's tiles rule
+// out; reads *count and nothing else when the list is empty.  Modes and grid
+// as launch_locate.
+hipError_t launch_locate_pair(const ApplyArgs& a, const uint8_t* ptab, const uint32_t* list, const uint32_t* count,
+                              uint32_t* pairs, int mode, bool skip, hipStream_t stream);
+// located[2 b], located[2 b + 1] = locate::resolve_pair(mismatch[b], single[b], pairs + b * words, k, p), b < nblk.
+hipError_t launch_locate_pair_resolve(const uint32_t* mismatch, const int32_t* single, const uint32_t* pairs,
+                                      int32_t* located, uint64_t nblk, unsigned k, unsigned p, hipStream_t stream);
+
 // The parity delta update kernel (gf_update.hip; shmr_ec_update_batch_dev):
 // one launch over pieces [0, npieces) of a piece table (update_plan.hpp
 // DevPiece, device memory), all of one round: no two of them store to the same

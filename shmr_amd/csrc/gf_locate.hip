@@ -32,6 +32,8 @@
 //    separate instantiation (locate_tiles<.., DEG>): the pattern's compare rows
 //    D in place of C, its blocks by stride or list, its row mask in the skip
 //    test; locate::resolve_checked.
+//  * Two damaged shards (shmr_ec_locate_pair_batch_dev, p >= 4): the preset,
+//    select, pair and pair resolve kernels further down, behind the chain above.
 //
 // Like the parity check kernels these are not gf_apply_kernel instantiations
 // and not part of shmr_ec_kernel_inventory.
@@ -266,7 +268,221 @@ hipError_t dispatch_locate_rows(const LocateArgs& la, unsigned rows, int mode, h
     }
 }
 
+// ---- two damaged shards (shmr_ec_locate_pair_batch_dev) --------------------
+// Behind the verify -> locate -> resolve chain above, for codecs with p >= 4
+// (locate_plan.hpp has the tests and the resolve rule):
+//  * preset: the pair bitmaps to all ones, the worklist counter to zero;
+//  * select: one thread per block; a block that no single shard explains, with
+//    at least three differing rows and every row beyond the group differing, is
+//    appended to the worklist (a vector global atomic add on the counter);
+//  * the pair kernel: the locate tile loop over count x tiles_per_block tiles,
+//    count read from device memory -- a clean batch costs the launch one word
+//    per workgroup; the 4-row plan and the pair tables staged once; per tile the
+//    4 syndrome chunks, then one ballot per candidate and one vector atomic AND
+//    per group of 32 candidates where any were eliminated.  `skip`: a wave first
+//    reads the group's bitmap word and leaves out candidates that are already
+//    cleared (bits only ever clear: a stale word costs work, never an answer);
+//  * resolve: one thread per block, locate::resolve_pair.
+
+struct PairArgs {
+    ApplyArgs a;             // the parity check launch of row group 0 (4 rows) over the whole batch
+    const uint8_t* ptab;     // the pair plan's tables, PermTab[pair_coeff_count(k)] (gf256.hpp Codec::locate_pair_plan)
+    const uint32_t* list;    // [count] the worklist: block indices, in any order
+    const uint32_t* count;   // its length, complete before this launch
+    uint32_t* pairs;         // [nblk][words] pair bitmaps, preset to all ones
+    uint32_t words;          // locate::pair_bitmap_words(k)
+    uint32_t skip;
+};
+
+// Whether rows v0, v1 of the syndrome are the coefficient multiples of row SRC
+// (0 for every byte that agrees).
+template <int SRC, int V0, int V1>
+__device__ __forceinline__ uint32_t pair_ratio_diff(const uint32_t (&s)[4][4], const Tab (&tq)[2]) {
+    uint32_t m[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) m[r][i] = 0u;
+    mac<2, 0>(m, u32x4{s[SRC][0], s[SRC][1], s[SRC][2], s[SRC][3]}, tq);
+    uint32_t d = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d |= (s[V0][i] ^ m[0][i]) | (s[V1][i] ^ m[1][i]);
+    return d;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void gf_locate_pair_kernel(const PairArgs pa) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    constexpr int TH = kThreads, R = 4;
+    const ApplyArgs& a = pa.a;
+    const uint32_t k = a.k;
+    const uint32_t tpb = a.tiles_per_block;
+    uint64_t count = as_const<cu32>(pa.count)[0];
+    if (count > a.nblk) count = a.nblk;   // (select appends a block once)
+    const uint64_t ntiles = count * tpb;
+    if (blockIdx.x >= ntiles) return;     // (workgroup-uniform; an empty worklist ends every workgroup here)
+    Ctx c{}, qc{};
+    stage_plan<R, TH, false>(a, a.plan, smem, c, 0);
+    {
+        u32x4* s_q = reinterpret_cast<u32x4*>(smem + ratio_tab_off(k, R));
+        const u32x4* gq = reinterpret_cast<const u32x4*>(pa.ptab);
+        for (uint32_t i = threadIdx.x; i < locate::pair_coeff_count(k) * 2; i += TH) s_q[i] = gq[i];
+        qc.s_tab = s_q;
+    }
+    __syncthreads();
+    const uint32_t ndd = locate::pair_dd_count(k), npairs = locate::pair_count(k);
+    const uint64_t tb = uint64_t(TH) * 16;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t j = tile / tpb, cc = tile - j * tpb;
+        uint64_t w = as_const<cu32>(pa.list)[j];
+        if (w >= a.nblk) continue;
+        const uint8_t* ib = a.in_base + w * a.in_bpitch;
+        const uint8_t* ob = a.out_base + w * a.out_bpitch;
+        uint32_t s[R][4];
+        locate_syndromes<R, MODE>(a, c, ib, ob, a.col_base + cc * tb + uint64_t(threadIdx.x) * 16, s);
+        uint32_t any = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) any |= s[r][0] | s[r][1] | s[r][2] | s[r][3];
+        // every lane of the wave is here (no lane leaves a tile early); no barrier follows
+        if (__builtin_amdgcn_ballot_w64(any != 0) == 0) continue;   // this wave's columns eliminate nobody
+        uint32_t* bw = pa.pairs + w * pa.words;
+        uint32_t keep = 0xffffffffu;   // wave-uniform: the survivors among candidates [i & ~31, i]
+        uint32_t live = 0xffffffffu;   // wave-uniform: the candidates of that group still to test
+        for (uint32_t i = 0; i < npairs; ++i) {
+            if ((i & 31u) == 0 && pa.skip)
+                live = uint32_t(__builtin_amdgcn_readfirstlane(int(__atomic_load_n(bw + (i >> 5), __ATOMIC_RELAXED))));
+            if ((live >> (i & 31u)) & 1u) {   // (a scalar branch: every lane of the wave takes it)
+                uint32_t d;
+                if (i < ndd) {   // data shards a < b: entries 4 i .. 4 i + 3 = al, be, ga, de
+                    Tab t01[2], t23[2];
+                    read_tabs<2>(qc, 2 * i, t01);
+                    read_tabs<2>(qc, 2 * i + 1, t23);
+                    const Tab of_s0[2] = {t01[0], t23[0]}, of_s1[2] = {t01[1], t23[1]};
+                    uint32_t m[2][4];
+#pragma unroll
+                    for (int r = 0; r < 2; ++r)
+#pragma unroll
+                        for (int x = 0; x < 4; ++x) m[r][x] = 0u;
+                    mac<2, 0>(m, u32x4{s[0][0], s[0][1], s[0][2], s[0][3]}, of_s0);
+                    mac<2, 0>(m, u32x4{s[1][0], s[1][1], s[1][2], s[1][3]}, of_s1);
+                    d = 0;
+#pragma unroll
+                    for (int x = 0; x < 4; ++x) d |= (s[2][x] ^ m[0][x]) | (s[3][x] ^ m[1][x]);
+                } else {         // data shard a with parity shard k + r: entries 4 ndd + 2 (a * 4 + r), + 1
+                    Tab tq[2];
+                    read_tabs<2>(qc, 2 * ndd + (i - ndd), tq);
+                    switch ((i - ndd) & 3u) {
+                        case 0: d = pair_ratio_diff<1, 2, 3>(s, tq); break;
+                        case 1: d = pair_ratio_diff<0, 2, 3>(s, tq); break;
+                        case 2: d = pair_ratio_diff<0, 1, 3>(s, tq); break;
+                        default: d = pair_ratio_diff<0, 1, 2>(s, tq); break;
+                    }
+                }
+                if (__builtin_amdgcn_ballot_w64(d != 0) != 0) keep &= ~(1u << (i & 31u));
+            }
+            if ((i & 31u) == 31u || i + 1 == npairs) {
+                if (keep != 0xffffffffu && (threadIdx.x & 63u) == 0) atomicAnd(bw + (i >> 5), keep);
+                keep = 0xffffffffu;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void gf_locate_pair_preset_kernel(uint32_t* pairs, uint64_t nwords,
+                                                                         uint32_t* count) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count = 0u;
+    for (uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x; i < nwords; i += uint64_t(gridDim.x) * kThreads)
+        pairs[i] = 0xffffffffu;
+}
+
+__global__ __launch_bounds__(kThreads) void gf_locate_pair_select_kernel(const uint32_t* mismatch, const int32_t* single,
+                                                                         uint32_t* list, uint32_t* count,
+                                                                         uint64_t nblk, uint32_t p) {
+    const uint64_t b = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+    if (b >= nblk) return;
+    if (locate::pair_listed(mismatch[b], single[b], p)) list[atomicAdd(count, 1u)] = uint32_t(b);
+}
+
+__global__ __launch_bounds__(kThreads) void gf_locate_pair_resolve_kernel(const uint32_t* mismatch,
+                                                                          const int32_t* single, const uint32_t* pairs,
+                                                                          int32_t* located, uint64_t nblk, uint32_t k,
+                                                                          uint32_t p) {
+    const uint64_t b = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+    if (b >= nblk) return;
+    int32_t out[2];
+    locate::resolve_pair(mismatch[b], single[b], pairs + b * locate::pair_bitmap_words(k), k, p, out);
+    located[2 * b] = out[0];
+    located[2 * b + 1] = out[1];
+}
+
+template <int MODE>
+hipError_t launch_pair_one(const PairArgs& pa, hipStream_t stream) {
+    const ApplyArgs& a = pa.a;
+    // (locate_plan.hpp restates the staged plan's size for the host)
+    if (ratio_tab_off(a.k, 4) != locate::pair_tab_off(a.k)) return hipErrorInvalidValue;
+    const size_t lds = locate::pair_lds_bytes(a.k);
+    uint64_t wgs = 0;
+    hipError_t e = locate_grid(&wgs);
+    if (e != hipSuccess) return e;
+    uint32_t grid = 0;
+    e = prepare_launch(reinterpret_cast<const void*>(gf_locate_pair_kernel<MODE>), lds, a.ntiles, &grid, wgs);
+    if (e != hipSuccess || grid == 0) return e;
+    hipLaunchKernelGGL((gf_locate_pair_kernel<MODE>), dim3(grid), dim3(kThreads), lds, stream, pa);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_locate_pair_preset(uint32_t* pairs, uint32_t* count, uint64_t nblk, unsigned k, hipStream_t stream) {
+    const uint64_t nwords = nblk * locate::pair_bitmap_words(k);
+    uint64_t grid = (nwords + kThreads - 1) / kThreads, cap = 0;
+    const hipError_t ge = locate_grid(&cap);
+    if (ge != hipSuccess) return ge;
+    if (grid > cap) grid = cap;
+    if (grid == 0) grid = 1;   // the counter
+    hipLaunchKernelGGL(gf_locate_pair_preset_kernel, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, pairs, nwords,
+                       count);
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_pair_select(const uint32_t* mismatch, const int32_t* single, uint32_t* list, uint32_t* count,
+                                     uint64_t nblk, unsigned p, hipStream_t stream) {
+    const uint64_t grid = (nblk + kThreads - 1) / kThreads;
+    if (grid == 0) return hipSuccess;
+    if (nblk > 0xffffffffull) return hipErrorInvalidValue;   // the worklist is 32-bit
+    hipLaunchKernelGGL(gf_locate_pair_select_kernel, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, mismatch, single,
+                       list, count, nblk, uint32_t(p));
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_pair(const ApplyArgs& a, const uint8_t* ptab, const uint32_t* list, const uint32_t* count,
+                              uint32_t* pairs, int mode, bool skip, hipStream_t stream) {
+    if (a.row0 != 0 || a.m < 4 || !locate::pair_supported(a.k, a.m)) return hipErrorInvalidValue;
+    PairArgs pa;
+    pa.a = a;
+    pa.ptab = ptab;
+    pa.list = list;
+    pa.count = count;
+    pa.pairs = pairs;
+    pa.words = locate::pair_bitmap_words(a.k);
+    pa.skip = skip ? 1u : 0u;
+    switch (mode) {
+        case 0: return launch_pair_one<0>(pa, stream);
+        case 1: return launch_pair_one<1>(pa, stream);
+        case 2: return launch_pair_one<2>(pa, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_locate_pair_resolve(const uint32_t* mismatch, const int32_t* single, const uint32_t* pairs,
+                                      int32_t* located, uint64_t nblk, unsigned k, unsigned p, hipStream_t stream) {
+    const uint64_t grid = (nblk + kThreads - 1) / kThreads;
+    if (grid == 0) return hipSuccess;
+    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gf_locate_pair_resolve_kernel, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, mismatch, single,
+                       pairs, located, nblk, uint32_t(k), uint32_t(p));
+    return hipGetLastError();
+}
 
 hipError_t launch_locate(const ApplyArgs& a, const uint8_t* qtab, const uint32_t* mismatch, uint32_t* cand,
                          unsigned rows, unsigned p, int mode, hipStream_t stream) {

@@ -329,6 +329,84 @@ class ReedSolomon:
         data, parity = self._split_shards(shards)
         return self.scrub_batch_dev(data, parity, shard_len=shard_len, device=device)
 
+    # -- scrub, parity >= 4: two damaged shards per block ---------------------------
+    def locate_pair_work_size(self, nblocks: int) -> int:
+        """Bytes of device scratch ``shmr_ec_locate_pair_batch_dev`` needs for
+        nblocks blocks; 0 for a codec it refuses."""
+        return int(self._L.shmr_ec_locate_pair_work_size(self._h, nblocks))
+
+    def locate_pair_batch_dev(self, data, parity, shard_len: Optional[int] = None, device: Optional[int] = None):
+        """Verify, locate, and locate pairs (``shmr_ec_locate_pair_batch_dev``):
+        data and parity as ``verify_batch_dev`` takes them; nothing but the
+        results is written.
+
+        Returns ``(mismatch [B], located [B, 2])``, two ``torch.int32`` tensors on
+        the tensors' device: the words of ``verify_batch_dev``, and per block
+        ``(locate_batch_dev's answer, -1)`` where that answer is not -2, the
+        ascending indices of the one pair of shards whose damage explains the
+        block, or ``(-2, -2)``.  Needs 4 <= p <= 32 and k <= 29
+        (``InvalidArgument`` otherwise).  The pair is exact for damage in two of
+        the k + 4 shards the first row group sees; with p = 4 damage in three
+        shards can pass for damage in two (shmr_ec.h).  Enqueued on torch's
+        current stream; not for graph capture, as ``locate_batch_dev``."""
+        import torch
+        B, dsp, dbp, psp, pbp, L = self._device_regions(data, parity, shard_len, "locate_pair_batch_dev")
+        mismatch = torch.empty(B, dtype=torch.int32, device=data.device)
+        located = torch.empty((B, 2), dtype=torch.int32, device=data.device)
+        work = torch.empty(self.locate_pair_work_size(B), dtype=torch.uint8, device=data.device)
+        dev, stream = self._stream_and_device(data)
+        dev = dev if device is None else int(device)
+        _check(self._L.shmr_ec_locate_pair_batch_dev(
+            self._h, ctypes.c_void_p(data.data_ptr()), dsp, dbp, ctypes.c_void_p(parity.data_ptr()), psp, pbp, B, L,
+            ctypes.c_void_p(mismatch.data_ptr()), ctypes.c_void_p(located.data_ptr()),
+            ctypes.c_void_p(work.data_ptr()), work.numel(), dev, stream))
+        return mismatch, located
+
+    def locate_pair_shards_dev(self, shards, shard_len: Optional[int] = None, device: Optional[int] = None):
+        """``locate_pair_batch_dev`` of one ``[B, k + p, pitch]`` tensor, as ``verify_shards_dev``."""
+        data, parity = self._split_shards(shards)
+        return self.locate_pair_batch_dev(data, parity, shard_len=shard_len, device=device)
+
+    def scrub_pair_batch_dev(self, data, parity, shard_len: Optional[int] = None, device: Optional[int] = None):
+        """The scrub for up to two damaged shards per block
+        (``shmr_ec_scrub_pair_batch_dev``), blocking: locate pairs, rebuild the
+        one or two located shards of each such block in place through the
+        reconstruct kernels, verify again.  Blocks that are not locatable are
+        not written.
+
+        Returns ``(located, counts)``: a numpy int32 ``[B, 2]`` as
+        ``locate_pair_batch_dev`` gives it, a rebuilt block that still differs
+        demoted to (-2, -2), and the tuple (clean, repaired in one shard,
+        repaired in two, not repairable).  Waits on torch's current stream; not
+        capturable."""
+        B, dsp, dbp, psp, pbp, L = self._device_regions(data, parity, shard_len, "scrub_pair_batch_dev")
+        located = np.zeros((B, 2), dtype=np.int32)
+        counts = (ctypes.c_uint64 * 4)()
+        dev, stream = self._stream_and_device(data)
+        _check(self._L.shmr_ec_scrub_pair_batch_dev(
+            self._h, ctypes.c_void_p(data.data_ptr()), dsp, dbp, ctypes.c_void_p(parity.data_ptr()), psp, pbp, B, L,
+            located.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), counts, dev if device is None else int(device),
+            stream))
+        return located, tuple(int(x) for x in counts)
+
+    def scrub_pair_shards_dev(self, shards, shard_len: Optional[int] = None, device: Optional[int] = None):
+        """``scrub_pair_batch_dev`` of one ``[B, k + p, pitch]`` tensor, as ``verify_shards_dev``."""
+        data, parity = self._split_shards(shards)
+        return self.scrub_pair_batch_dev(data, parity, shard_len=shard_len, device=device)
+
+    def locate_pair_plan(self):
+        """``(npairs, dd, dp)`` of what the pair kernel multiplies by
+        (``shmr_ec_locate_pair_plan``): the candidate count, a uint8
+        ``[k (k - 1) / 2, 4]`` of the data-data pairs' coefficients in
+        lexicographic ``(a, b)`` order and a uint8 ``[k, 4, 2]`` of the
+        data-parity pairs' ratios at ``[a, r]``."""
+        k = self.data_shard_count()
+        ndd = k * (k - 1) // 2
+        coeffs = np.zeros(4 * ndd + 8 * k, dtype=np.uint8)
+        n = ctypes.c_uint32()
+        _check(self._L.shmr_ec_locate_pair_plan(self._h, _ptr(coeffs), coeffs.size, ctypes.byref(n)))
+        return int(n.value), coeffs[:4 * ndd].reshape(ndd, 4).copy(), coeffs[4 * ndd:].reshape(k, 4, 2).copy()
+
     # -- parity delta update: writes into device-resident blocks -------------------
     _UPDATE_DTYPE = np.dtype([("block", "<u4"), ("shard", "<u4"), ("offset", "<u8"), ("len", "<u8"),
                               ("src_offset", "<u8")], align=True)
