@@ -549,6 +549,85 @@ int shmr_ec_read_plan(shmr_ec_t* rs, const uint8_t* present, size_t nblocks, siz
                       const shmr_ec_read* reads, size_t nreads, size_t dst_bytes,
                       uint8_t* rebuilt, uint32_t* npieces, uint32_t* nchunks);
 
+/* ---- parity delta update of degraded device-resident blocks ------------------- *
+ * The write half of shmr_ec_read_batch_dev: shmr_ec_update_batch_dev for blocks
+ * with absent shards, without rebuilding them first.  The code is linear and
+ * column-wise, so for every update of columns [a, b) = [offset, offset + len)
+ * of data shard j = `shard` of block B = `block`:
+ *   - shard j present: data_j[col] becomes d_src[src_offset + col - a], and
+ *     every PRESENT parity row r of B gets parity_r[col] ^= C[r][j] * (old[col]
+ *     ^ new[col]); absent parity slots are skipped (traffic (3 + 2 p') * len,
+ *     p' the present parity rows);
+ *   - shard j absent: old[col] is the sum over t of D[j][t] * input_t[col], the
+ *     bytes shmr_ec_reconstruct_batch_dev(..., data_only = 1) would leave in the
+ *     shard -- the inputs the first `data` present shards in index order (the
+ *     crate's rule; parity shards can be inputs), D the row that
+ *     shmr_ec_reconstruct_plan gives for the pattern.  delta = old ^ new goes
+ *     into every present parity row as above; slot j stays absent and is not
+ *     touched (traffic (data + 1 + 2 p') * len).  Afterwards the survivors are
+ *     the punctured codeword of the new data: any later reconstruct or read
+ *     returns the new bytes.
+ * Byte-exact footprint: only bytes [a, b) of shard j (if present) and of the
+ * present parity shards of B are stored; absent slots are never read and never
+ * written; the pitch padding past shard_len, the other shards and the other
+ * blocks keep their bytes.  A block with every shard present gets exactly the
+ * bytes shmr_ec_update_batch_dev writes.
+ * Damage is preserved: what is XORed into the present shards is the punctured
+ * codeword of delta, so the surplus-row word of
+ * shmr_ec_reconstruct_checked_batch_dev is the same before and after.  NOT
+ * checked: the survivors.  A damaged survivor among the inputs goes into `old`
+ * as a plain reconstruct would rebuild it; shmr_ec_reconstruct_checked_batch_dev
+ * and shmr_ec_locate_checked_batch_dev are the calls that look.
+ * Several updates of one block over intersecting columns, of present and absent
+ * shards in any mix, are ordered by the call itself with the round rule of
+ * shmr_ec_update_rounds (same block, disjoint columns: same round).  The result
+ * does not depend on the order of the rounds: each round leaves the survivors
+ * a punctured codeword plus the original damage.
+ *
+ * Applies nupdates updates (HOST array, the struct of shmr_ec_update_batch_dev)
+ * to nblocks blocks addressed exactly as shmr_ec_read_batch_dev: all total
+ * shards at one pitch, `present` HOST flags, nblocks x total, one pattern per
+ * block (blocks of different patterns share a launch).  d_src: src_bytes bytes
+ * of DEVICE memory on `device` holding the new bytes.  d_src MUST NOT overlap
+ * the shards (the caller's contract: it is not checked, and the result of an
+ * overlap is undefined).  Any alignment of the base, pitches, offset and
+ * src_offset and any code shmr_ec_update_batch_dev takes (parity >= 1) is
+ * accepted.
+ * Checked in this order, all before any device work: NULL rs
+ * (INVALID_ARGUMENT); nupdates == 0 or nblocks == 0 (OK, nothing enqueued);
+ * shard_len == 0 (EMPTY_SHARD); a NULL pointer, `present` included
+ * (INVALID_ARGUMENT); the per-update range checks and the intersecting-ranges
+ * check of shmr_ec_update_batch_dev (INVALID_ARGUMENT); a block, updated or
+ * not, with fewer than `data` present shards (TOO_FEW_SHARDS_PRESENT); the
+ * device.
+ * Stream-ordered, no host readback; after the first call on a device no
+ * blocking call of the library's own.  NOT capturable: a `stream` that is being
+ * captured into a graph is refused with INVALID_ARGUMENT and nothing is
+ * enqueued.  One launch per round per table chunk
+ * (shmr_ec_update_degraded_plan), counted under SHMR_EC_DEV_LAUNCHES.
+ * Measured on RS(8,3) x 4 MiB x 512 blocks with one data shard lost per block,
+ * against shmr_ec_reconstruct_batch_dev + shmr_ec_update_batch_dev: a write into
+ * the lost shard is 4.6x faster at 4 KiB, 4.1x at 64 KiB and 1.12x at the whole
+ * shard; rebuilding first is never faster, up to all `data` shards of every
+ * block (1.03x).  A cache that rewrites most of a block
+ * should rebuild and re-encode it instead, as for shmr_ec_update_batch_dev. */
+int shmr_ec_update_degraded_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard_pitch,
+                                      size_t block_pitch, const uint8_t* present, size_t nblocks,
+                                      size_t shard_len, const shmr_ec_update* updates,
+                                      size_t nupdates, const uint8_t* d_src, size_t src_bytes,
+                                      int device, void* stream);
+
+/* Host only; for tests and tools (as shmr_ec_read_plan): the checks of
+ * shmr_ec_update_degraded_batch_dev on the list and the flags, in its order,
+ * then the rounds as shmr_ec_update_rounds reports them (round_of: nupdates
+ * entries), per update whether its shard is absent (rebuilt: nupdates entries,
+ * 0 present / 1 absent), the number of kernel pieces and the number of table
+ * chunks the list uploads in.  Any out pointer may be NULL. */
+int shmr_ec_update_degraded_plan(shmr_ec_t* rs, const uint8_t* present, size_t nblocks,
+                                 size_t shard_len, const shmr_ec_update* updates, size_t nupdates,
+                                 size_t src_bytes, uint32_t* round_of, uint32_t* nrounds,
+                                 uint8_t* rebuilt, uint32_t* npieces, uint32_t* nchunks);
+
 /* ---- checked reconstruct: verify the spare shards while rebuilding ----------- *
  * shmr_ec_reconstruct_batch_dev reads the first `data` present shards of a
  * block and never looks at the other present ones; shmr_ec_verify_batch_dev

@@ -7,8 +7,10 @@ of GF(2^8) arithmetic runs in hand-written gfx950 HIP kernels
 
 Beyond the crate's calls, ``ReedSolomon`` serves device-resident blocks:
 batch encode / reconstruct / verify, scrub and checked reconstruct, writes
-that keep the parity valid (``update_batch_dev``) and ranged reads, lost shards
-included (``read_batch_dev``, ``read_plan``, ``block_range_reads``).
+that keep the parity valid (``update_batch_dev``; into blocks with lost shards
+``update_degraded_batch_dev``, ``update_degraded_plan``, ``block_range_writes``)
+and ranged reads, lost shards included (``read_batch_dev``, ``read_plan``,
+``block_range_reads``).
 """
 from .reed_solomon import (DeviceBuffer, Error, Op, capture_reserve, PinnedBuffer, ReedSolomon, ShardPool, ShardSlab, calculate_shard_size, describe_variant, device_count,  # noqa: F401
                            device_init, device_stats, get_tuning, host_register, host_unregister, kernel_inventory,

@@ -87,6 +87,12 @@ SIGNATURES = [
     ("shmr_ec_read_plan", ctypes.c_int,
      [ctypes.c_void_p, _u8p, _sz, _sz, ctypes.c_void_p, _sz, _sz, _u8p, ctypes.POINTER(ctypes.c_uint32),
       ctypes.POINTER(ctypes.c_uint32)]),
+    ("shmr_ec_update_degraded_batch_dev", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_void_p, _sz, ctypes.c_void_p, _sz,
+      ctypes.c_int, ctypes.c_void_p]),
+    ("shmr_ec_update_degraded_plan", ctypes.c_int,
+     [ctypes.c_void_p, _u8p, _sz, _sz, ctypes.c_void_p, _sz, _sz, ctypes.POINTER(ctypes.c_uint32),
+      ctypes.POINTER(ctypes.c_uint32), _u8p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     ("shmr_ec_reconstruct_checked_batch_dev", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _u8p, _sz, _sz, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
       ctypes.c_void_p]),

@@ -655,6 +655,20 @@ int read_checks(const Codec& c, bool pointers, const uint8_t* present, size_t nb
     return core::validate_presence(c, present, nblocks);
 }
 
+// The host checks of a degraded update behind rs, the empty call and shard_len,
+// in the header's order: the pointers, the updates and their intersections (the
+// rounds, and with `pieces` the pieces, come out of the same pass), then every
+// block's presence flags.
+int update_degraded_checks(const Codec& c, bool pointers, const uint8_t* present, size_t nblocks, size_t shard_len,
+                           const shmr_ec_update* updates, size_t nupdates, size_t src_bytes, shmr::update::Plan* up,
+                           bool pieces) {
+    if (!pointers || !present || !updates ||
+        !shmr::update::plan(updates, nupdates, nblocks, c.k(), shard_len, src_bytes, up, pieces))
+        return SHMR_EC_INVALID_ARGUMENT;
+    return shmr::degraded::enough_present(present, nblocks, c.k(), c.k() + c.p()) ? SHMR_EC_OK
+                                                                                   : SHMR_EC_TOO_FEW_SHARDS_PRESENT;
+}
+
 // The flags of the checked calls that this build knows.
 constexpr int kCheckFlags = SHMR_EC_CHECK_DATA_ONLY | SHMR_EC_CHECK_NO_REBUILD;
 
@@ -1230,6 +1244,53 @@ int shmr_ec_read_plan(shmr_ec_t* rs, const uint8_t* present, size_t nblocks, siz
         if (pieces.size() > 0xffffffffull) return SHMR_EC_INVALID_ARGUMENT;
         *npieces = uint32_t(pieces.size());
         *nchunks = shmr::read::count_chunks(pieces);
+        return SHMR_EC_OK;
+    });
+}
+
+// ---- parity delta update of degraded device-resident blocks --------------------------
+int shmr_ec_update_degraded_batch_dev(shmr_ec_t* rs, uint8_t* d_shards, size_t shard_pitch, size_t block_pitch,
+                                      const uint8_t* present, size_t nblocks, size_t shard_len,
+                                      const shmr_ec_update* updates, size_t nupdates, const uint8_t* d_src,
+                                      size_t src_bytes, int device, void* stream) {
+    return guarded([&]() -> int {
+        if (!rs) return SHMR_EC_INVALID_ARGUMENT;
+        if (nupdates == 0) return SHMR_EC_OK;
+        Codec& c = *rs->codec;
+        shmr::update::Plan up;
+        auto check = [&] {
+            return update_degraded_checks(c, d_shards && d_src, present, nblocks, shard_len, updates, nupdates, src_bytes,
+                                          &up, true);
+        };
+        return batch_dev(nblocks, shard_len, device, check, [&] {
+            return core::update_degraded_on_device(c, device, d_shards, shard_pitch, block_pitch, present, up, d_src,
+                                                   static_cast<hipStream_t>(stream));
+        });
+    });
+}
+
+int shmr_ec_update_degraded_plan(shmr_ec_t* rs, const uint8_t* present, size_t nblocks, size_t shard_len,
+                                 const shmr_ec_update* updates, size_t nupdates, size_t src_bytes, uint32_t* round_of,
+                                 uint32_t* nrounds, uint8_t* rebuilt, uint32_t* npieces, uint32_t* nchunks) {
+    return guarded_light([&]() -> int {
+        if (!rs) return SHMR_EC_INVALID_ARGUMENT;
+        for (uint32_t* out : {nrounds, npieces, nchunks})
+            if (out) *out = 0;
+        if (nupdates == 0 || nblocks == 0) return SHMR_EC_OK;
+        if (shard_len == 0) return SHMR_EC_EMPTY_SHARD;
+        const Codec& c = *rs->codec;
+        shmr::update::Plan up;
+        const int rc = update_degraded_checks(c, true, present, nblocks, shard_len, updates, nupdates, src_bytes, &up,
+                                              npieces || nchunks);
+        if (rc) return rc;
+        const size_t t = c.k() + c.p();
+        if (round_of) std::copy(up.round_of.begin(), up.round_of.end(), round_of);
+        if (nrounds) *nrounds = up.nrounds;
+        if (rebuilt)
+            for (size_t i = 0; i < nupdates; ++i) rebuilt[i] = present[updates[i].block * t + updates[i].shard] ? 0 : 1;
+        if (up.pieces.size() > 0xffffffffull) return SHMR_EC_INVALID_ARGUMENT;
+        if (npieces) *npieces = uint32_t(up.pieces.size());
+        if (nchunks) *nchunks = shmr::degraded::count_chunks(up.pieces);
         return SHMR_EC_OK;
     });
 }

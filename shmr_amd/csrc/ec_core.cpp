@@ -1468,6 +1468,100 @@ int read_on_device(Codec& c, int dev, const uint8_t* d_shards, uint64_t shard_pi
         });
 }
 
+// ===========================================================================
+// Parity delta update of degraded blocks.  Every pattern of an updated block
+// gets its present-parity-row list on the device, and the pattern of a block
+// with an updated absent shard its data-only reconstruct plan as the read above
+// (its rows are exactly the absent data shards, ascending); then the pieces go
+// out as the update's: in round order, the pieces of each round in a table
+// chunk one launch.
+// ===========================================================================
+int update_degraded_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch, uint64_t block_pitch,
+                              const uint8_t* present, const update::Plan& up, const uint8_t* d_src,
+                              hipStream_t stream) {
+    static_assert(degraded::kTablePieces * sizeof(degraded::DevPiece) <= UploadRing::kSlotBytes,
+                  "one ring slot per chunk");
+    int rc = refuse_capture(dev, stream);
+    if (rc) return rc;
+    const unsigned k = c.k(), t = k + c.p();
+    Plan& enc = *c.encode_plan();
+    const uint8_t* denc = nullptr;
+    rc = plan_on_device(enc, dev, stream, false, &denc);
+    if (rc) return rc;
+    // the row list of every piece, and the plan image and plan row of every rebuild piece, per pattern and per block
+    struct Pattern {
+        std::vector<uint8_t> key;
+        const uint8_t* drows = nullptr;
+        const uint8_t* dplan = nullptr;   // on the first updated absent shard
+        std::vector<uint32_t> row_of;     // by data shard
+    };
+    std::map<std::vector<uint8_t>, Pattern> patterns;
+    std::map<uint32_t, Pattern*> of_block;
+    const std::vector<update::Piece>& ps = up.pieces;
+    for (const update::Piece& p : ps) {
+        const uint8_t* pr = present + uint64_t(p.block) * t;
+        auto ob = of_block.find(p.block);
+        if (ob == of_block.end()) {
+            std::vector<uint8_t> key(t);
+            for (unsigned i = 0; i < t; ++i) key[i] = pr[i] ? 1 : 0;
+            auto it = patterns.find(key);
+            if (it == patterns.end()) {
+                Pattern pat;
+                pat.key = key;
+                rc = plan_on_device(*c.parity_rows_plan(key), dev, stream, false, &pat.drows);
+                if (rc) return rc;
+                it = patterns.emplace(std::move(key), std::move(pat)).first;
+            }
+            ob = of_block.emplace(p.block, &it->second).first;
+        }
+        Pattern& pat = *ob->second;
+        if (pr[p.shard] || pat.dplan) continue;
+        const std::shared_ptr<Plan> plan = c.reconstruct_plan(pat.key, true);
+        rc = plan_on_device(*plan, dev, stream, false, &pat.dplan);
+        if (rc) return rc;
+        pat.row_of.assign(k, 0);
+        for (unsigned r = 0; r < plan->m; ++r) pat.row_of[plan->out_idx[r]] = r;
+    }
+    const bool base16 = aligned16(uintptr_t(d_shards)) && aligned16(shard_pitch) && aligned16(block_pitch);
+    kern::UpdateDegradedArgs u{};
+    u.shards = d_shards;
+    u.src = d_src;
+    u.tabs = denc + plan_tab_off(enc.k, enc.m);
+    u.bpitch = block_pitch;
+    u.spitch = shard_pitch;
+    u.k = k;
+    u.p = enc.m;
+    return with_piece_tables<degraded::DevPiece>(
+        dev, stream, ps, d_src, base16,
+        [&](const update::Piece& p, uint32_t vec, uint32_t tile0) {
+            const Pattern& pat = *of_block.find(p.block)->second;
+            const uint64_t rows = uint64_t(uintptr_t(pat.drows));
+            if (present[uint64_t(p.block) * t + p.shard])
+                return degraded::DevPiece{p.col, p.flat, 0, rows, p.block, p.len, p.shard | vec, tile0};
+            return degraded::DevPiece{p.col,   p.flat, uint64_t(uintptr_t(pat.dplan)),
+                                      rows,    p.block, p.len,
+                                      degraded::pack_shard(p.shard, pat.row_of[p.shard], true) | vec,
+                                      tile0};
+        },
+        [&](const degraded::DevPiece* d, size_t c0, size_t cnt, uint32_t) -> int {
+            uint32_t tile0 = 0;
+            for (size_t i = 0; i < cnt;) {   // the chunk's pieces of one round
+                size_t j = i;
+                uint32_t nt = 0;
+                for (; j < cnt && ps[c0 + j].round == ps[c0 + i].round; ++j) nt += update::piece_tiles(ps[c0 + j].len);
+                u.pieces = d + i;
+                u.npieces = uint32_t(j - i);
+                u.tile_base = tile0;
+                u.ntiles = nt;
+                count_device(dev, kDevLaunches);
+                SHMR_HIP_TRY(kern::launch_update_degraded(u, stream));
+                tile0 += nt;
+                i = j;
+            }
+            return SHMR_EC_OK;
+        });
+}
+
 int validate_presence(const Codec& c, const uint8_t* present, uint64_t nblocks) {
     const unsigned k = c.k(), t = k + c.p();
     for (uint64_t b = 0; b < nblocks; ++b) {

@@ -18,6 +18,7 @@
 #include "gf_apply.hpp"
 #include "read_plan.hpp"
 #include "shmr_ec.h"
+#include "update_degraded_plan.hpp"
 #include "update_plan.hpp"
 
 namespace shmr {
@@ -322,6 +323,21 @@ int update_on_device(Codec& c, int dev, const Layout& L, const update::Plan& up,
 // (INVALID_ARGUMENT, nothing enqueued).  Nothing but d_dst is written.
 int read_on_device(Codec& c, int dev, const uint8_t* d_shards, uint64_t shard_pitch, uint64_t block_pitch,
                    const uint8_t* present, const std::vector<read::Piece>& ps, uint8_t* d_dst, hipStream_t stream);
+// Parity delta update of degraded blocks (shmr_ec_update_degraded_batch_dev):
+// the planned pieces `up` (update_plan.hpp, validated by the caller, as
+// `present` is) applied to blocks laid out as for reconstruct_on_device below,
+// the new bytes read from d_src.  A piece names the device image of its
+// pattern's present parity rows (Codec::parity_rows_plan), and a piece of an
+// absent shard that of the pattern's data-only reconstruct plan and its row
+// there (the per-pattern cache, uploaded on `stream` on first use); blocks of
+// different patterns share a launch.  The piece table travels as
+// update_on_device's: the chunks of piece::chunk_pieces, behind each chunk one
+// launch per round present in it.  Stream-ordered, no blocking call after
+// device init; a stream that is being captured is refused (INVALID_ARGUMENT,
+// nothing enqueued).  Absent slots are neither read nor written.
+int update_degraded_on_device(Codec& c, int dev, uint8_t* d_shards, uint64_t shard_pitch, uint64_t block_pitch,
+                              const uint8_t* present, const update::Plan& up, const uint8_t* d_src,
+                              hipStream_t stream);
 // The blocks slots[0 .. n) (ascending, distinct) of a single-plan launch set.
 int launch_slots(Plan& plan, int dev, const Layout& L, const uint64_t* slots, uint64_t n, uint64_t len,
                  hipStream_t stream, OpClass op);

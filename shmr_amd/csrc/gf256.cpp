@@ -327,6 +327,25 @@ std::shared_ptr<Plan> Codec::locate_checked_plan(const std::vector<uint8_t>& pre
     return lp;
 }
 
+std::shared_ptr<Plan> Codec::parity_rows_plan(const std::vector<uint8_t>& present) {
+    // (key[t + 1] = 5: never a key of the plans above)
+    const unsigned t = k_ + p_;
+    std::vector<uint8_t> key(t + 2, 0);
+    for (unsigned i = 0; i < t; ++i) key[i] = present[i] ? 1 : 0;
+    key[t + 1] = 5;
+    std::lock_guard<std::mutex> lock(mu_);
+    auto found = plans_.find(key);
+    if (found != plans_.end()) return found->second;
+    auto rp = std::make_shared<Plan>();
+    rp->in_idx.reserve(1);   // (Plan::image copies 0 inputs: no null source)
+    for (unsigned r = 0; r < p_; ++r)
+        if (key[k_ + r]) rp->out_idx.push_back(uint16_t(r));
+    rp->m = unsigned(rp->out_idx.size());
+    rp->rows = Matrix(rp->m, 0);
+    plans_[key] = rp;
+    return rp;
+}
+
 std::shared_ptr<Codec> get_codec(unsigned k, unsigned p) {
     // Leaked on purpose: codecs own device images that must outlive every
     // in-flight kernel, and HIP may already be torn down at static exit.

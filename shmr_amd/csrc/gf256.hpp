@@ -138,6 +138,13 @@ public:
     // (no pattern of this matrix has one).  Cached per pattern.
     std::shared_ptr<Plan> locate_checked_plan(const std::vector<uint8_t>& present, bool* singular = nullptr);
 
+    // The present parity rows of a presence pattern (present.size() == k+p) in
+    // the shape of a plan without inputs: k = 0, out_idx the rows r (0-based,
+    // shard k + r present) in ascending order, no tables -- the device image
+    // is [u32 0][u32 n][u16 row[n]] padded to 32 B.  What the degraded update
+    // walks (update_degraded_plan.hpp).  Cached per pattern.
+    std::shared_ptr<Plan> parity_rows_plan(const std::vector<uint8_t>& present);
+
     uint64_t decode_cache_hits() const { return hits_; }
     uint64_t decode_cache_misses() const { return misses_; }
 

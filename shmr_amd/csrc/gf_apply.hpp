@@ -12,6 +12,9 @@ struct DevPiece;   // update_plan.hpp
 namespace read {
 struct DevPiece;   // read_plan.hpp
 }
+namespace degraded {
+struct DevPiece;   // update_degraded_plan.hpp
+}
 namespace kern {
 
 constexpr int kThreads = 256;                          // lanes per workgroup (4 waves)
@@ -420,6 +423,31 @@ struct ReadArgs {
     uint32_t k, npieces, ntiles;
 };
 hipError_t launch_read(const ReadArgs& r, hipStream_t stream);
+
+// The degraded update kernel (gf_update_degraded.hip;
+// shmr_ec_update_degraded_batch_dev): one launch over pieces [0, npieces) of a
+// piece table (update_degraded_plan.hpp DevPiece, device memory), all of one
+// round: no two of them touch the same column of one block.  One workgroup per
+// 4 KiB tile of a piece; tile_base = the first piece's tile0, ntiles = the
+// tiles of these pieces (< 2^31).  All shards of block b at shards + b *
+// bpitch + i * spitch.  tabs: the PermTab[k][p] tables of the codec's encode
+// plan image (entry j * p + r).  A piece of a present shard loads and stores
+// bytes [col, col + len) of it; a rebuild piece (kRebuildFlag) loads those
+// columns of the k inputs its plan image names (DevPiece::plan, a data-only
+// reconstruct plan image, and its row there) and leaves the shard's slot alone.
+// Either loads len bytes of src and loads and stores bytes [col, col + len) of
+// the parity rows DevPiece::rows lists (the block's present ones), nothing
+// else.  A piece without kVecFlag moves byte by byte, as in launch_update.
+// Not part of kernel_inventory.
+struct UpdateDegradedArgs {
+    uint8_t* shards;
+    const uint8_t* src;
+    const uint8_t* tabs;
+    const degraded::DevPiece* pieces;
+    uint64_t bpitch, spitch;
+    uint32_t k, p, npieces, tile_base, ntiles;
+};
+hipError_t launch_update_degraded(const UpdateDegradedArgs& u, hipStream_t stream);
 
 // The submission queue's completion mark (submit.cpp): a one-wave kernel on
 // `stream` that stores `seq` to `word` -- pinned host memory, a system-scope

@@ -583,6 +583,78 @@ class ReedSolomon:
                                               shards.stride(0), _ptr(pr), B, L, ctypes.c_void_p(ra.ctypes.data),
                                               len(ra), ctypes.c_void_p(dst.data_ptr()), dst.numel(), dev, stream))
 
+    # -- parity delta update of degraded device-resident blocks ----------------------
+    @staticmethod
+    def block_range_writes(block: int, pos: int, length: int, shard_len: int, src_offset: int = 0) -> list:
+        """The updates of a ``VirtualBlock::write(pos, buf)``, the write-side twin
+        of ``block_range_reads``: bytes [pos, pos + length) of the block's
+        payload split at shard boundaries into ``(block, shard, offset, length,
+        src_offset)`` tuples whose sources follow one another from
+        ``src_offset``.  Pure: the caller keeps the range inside the payload
+        (shard < data is checked by the update calls)."""
+        block, pos, length, shard_len, src_offset = (int(x) for x in (block, pos, length, shard_len, src_offset))
+        if block < 0 or pos < 0 or length < 0 or shard_len <= 0 or src_offset < 0:
+            raise ValueError("block, pos, length and src_offset must be >= 0 and shard_len > 0")
+        return ReedSolomon.block_range_reads(block, pos, length, shard_len, src_offset)
+
+    def update_degraded_plan(self, present: np.ndarray, updates, shard_len: int, src_bytes: int):
+        """``shmr_ec_update_degraded_plan`` (host only): the checks
+        ``update_degraded_batch_dev`` makes on the list and on ``present`` (host
+        flags ``[B, total]``), then ``(round_of, nrounds, rebuilt, npieces,
+        nchunks)``: the rounds as ``update_rounds`` gives them, a numpy uint8
+        array with 1 for every update whose shard is absent, the number of
+        kernel pieces, and the number of table chunks of the list."""
+        t = self.total_shard_count()
+        pr = np.ascontiguousarray(present, dtype=np.uint8)
+        if pr.size % t:
+            raise ValueError(f"present must hold {t} flags per block")
+        ua = self._update_array(updates)
+        round_of = np.zeros(len(ua), dtype=np.uint32)
+        rebuilt = np.zeros(len(ua), dtype=np.uint8)
+        nrounds, npieces, nchunks = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(self._L.shmr_ec_update_degraded_plan(
+            self._h, _ptr(pr), pr.size // t, shard_len, ctypes.c_void_p(ua.ctypes.data), len(ua), src_bytes,
+            round_of.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(nrounds), _ptr(rebuilt),
+            ctypes.byref(npieces), ctypes.byref(nchunks)))
+        return round_of, int(nrounds.value), rebuilt, int(npieces.value), int(nchunks.value)
+
+    def update_degraded_batch_dev(self, shards, present: np.ndarray, updates, src, shard_len: Optional[int] = None,
+                                  device: Optional[int] = None) -> None:
+        """``update_batch_dev`` for blocks with lost shards, without rebuilding
+        them first (``shmr_ec_update_degraded_batch_dev``): shards and present as
+        ``read_batch_dev`` takes them (same checks in the same order); ``src`` a
+        1-D uint8 tensor on the same GPU holding the new bytes, which must not
+        overlap shards.  For every ``(block, shard, offset, length,
+        src_offset)`` of ``updates``: if the data shard is present its bytes
+        [offset, offset + length) become ``src[src_offset : src_offset +
+        length]``; if it is absent, the old bytes are rebuilt from those columns
+        of the first k present shards -- what ``reconstruct_batch_dev(data_only=
+        True)`` would leave there -- and its slot is not touched.  Either way
+        every present parity row changes by C[r][shard] (x) (old ^ new) on
+        those columns, so the survivors stay the punctured codeword of the new
+        data; absent slots are neither read nor written, and nothing else is.
+        Survivors are not checked for damage, and damage is preserved
+        (``reconstruct_checked_batch_dev`` looks).  Enqueued on torch's current
+        stream; not for graph capture (the native call refuses a stream that
+        is being captured)."""
+        if shards.dim() != 3:
+            raise TypeError("shards must be a [blocks, total, bytes] tensor")
+        B, t = shards.shape[0], self.total_shard_count()
+        L = shard_len if shard_len is not None else shards.stride(1)
+        self._check_batch_tensor(shards, t, shards.stride(1), L)
+        pr = np.ascontiguousarray(present, dtype=np.uint8)
+        if pr.size != B * t:
+            raise ValueError(f"present must hold {B} x {t} flags")
+        pr = pr.reshape(B, t)
+        self._check_addressable(shards)
+        self._flat_u8_on(src, "src", shards)
+        ua = self._update_array(updates)
+        dev, stream = self._stream_and_device(shards)
+        dev = dev if device is None else int(device)
+        _check(self._L.shmr_ec_update_degraded_batch_dev(
+            self._h, ctypes.c_void_p(shards.data_ptr()), shards.stride(1), shards.stride(0), _ptr(pr), B, L,
+            ctypes.c_void_p(ua.ctypes.data), len(ua), ctypes.c_void_p(src.data_ptr()), src.numel(), dev, stream))
+
     # -- device-resident batches (torch tensors on the GPU) ------------------------
     @staticmethod
     def _check_batch_tensor(t, rows: int, shard_pitch: int, shard_len: int) -> None:
